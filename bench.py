@@ -8,6 +8,17 @@ roofline, d=256, 1/2/4/8 GPU".
 With --gpus N > 1 and no launcher (WORLD_SIZE unset) bench.py starts the N
 rank processes itself (spawn_ranks); under a launcher WORLD_SIZE must equal N.
 
+A plain run does what the headline needs and no more: it builds the inputs,
+warms up, times the K steps and prints the line.  --full adds everything
+measured or checked next to it, each in runs of its own: the CPU baseline and
+its bitwise parity check, the training-mode aggregation (DropEdge p=0.3
+forward + backward), the given-order A/B of a degree-ordered graph, at N>1
+the halo breakdown in both directions (and with it the aggregation-alone time
+the roofline is computed from), and, asked for by name, --extras and
+--c4-reference.  --dump-outputs DIR writes what the last timed step computed
+(the rank's Z, or a fixed seeded sample of its rows) as DIR/<name>.npy; the
+inputs are seeded, so two builds can be compared output for output.
+
 Workloads (BASELINE.json configs):
   C3 (default at N=1)  seeded Erdos-Renyi typed graph, N=1M, avg total
                        out-degree 32 over L=6 edge types (dedupe), d=256.
@@ -73,13 +84,23 @@ def parse():
                          "one-time preprocessing of the graph); auto = degree for R-MAT, given for ER")
     ap.add_argument("--chunks", type=int, default=0,
                     help="N>1: column slices of the pipelined halo exchange (0 = d/128; 1 = serial)")
-    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget (0 disables)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run what is measured or checked next to the headline: the CPU "
+                         "baseline and bitwise parity (--cpu-seconds), the DropEdge p=0.3 training-mode forward + "
+                         "backward, the given-order A/B of a degree-ordered graph, the N>1 halo breakdown; "
+                         "--extras and --c4-reference add theirs to such a run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (float32): Z, "
+                         "this rank's aggregated rows (Z_rank<r> at N>1), whole when small, otherwise a fixed "
+                         "seeded sample of its rows (at most 32 MiB over all ranks)")
+    ap.add_argument("--cpu-seconds", type=float, default=10.0, help="--full: CPU baseline budget (0 disables)")
     ap.add_argument("--c4-reference", action="store_true",
-                    help="N=1 C3 line: also time BASELINE's C4 graph whole on the one GPU (the N>1 lines' per-GPU "
-                         "baseline; off by default: its launches are the headline kernel's and would skew the "
+                    help="--full, N=1 C3 line: also time BASELINE's C4 graph whole on the one GPU (the N>1 lines' "
+                         "per-GPU baseline; by name only: its launches are the headline kernel's and would skew the "
                          "rocprofv3 average of that kernel)")
     ap.add_argument("--extras", action="store_true",
-                    help="also time fused-DropEdge fwd, backward, MFMA linear and a full layer (not the headline)")
+                    help="--full: also time fused-DropEdge fwd, backward, MFMA linear and a full layer (not the "
+                         "headline)")
     ap.add_argument("--dist-backend", default="nccl",
                     help="process-group backend for N>1 (nccl = RCCL; gloo only to smoke-test the N>1 path "
                          "with several ranks on one GPU)")
@@ -89,7 +110,12 @@ def parse():
     ap.add_argument("--only", choices=["fwd", "bwd", "linear", "layer", "infer", "c1", "model"], default=None,
                     help="profiling aid: run just that kernel K times (no JSON line); c1: print the C1 "
                          "(debug.json model) timings alone")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if (args.extras or args.c4_reference) and not args.full:
+        ap.error("--extras and --c4-reference add to a --full run: pass --full with them")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error(f"--steps must be >= 1 and --warmup >= 0 (got {args.steps}, {args.warmup})")
+    return args
 
 
 def resolve_workload(args, world):
@@ -292,7 +318,7 @@ def main():
     if node_order == "degree" and world == 1:
         from grl.graph import degree_order
 
-        if args.only is None:  # (a profiled run keeps only the timed kernel's launches)
+        if args.only is None and args.full:  # (a plain or a profiled run keeps only the timed kernel's launches)
             order_ab = {"given_ms": _time(lambda: spmm_forward(X_loc, graph.with_dropedge(de)), 3)}
         t1 = time.time()
         graph, perm = degree_order(graph)
@@ -341,10 +367,15 @@ def main():
     surface("timed region", dev)
     per_step = [a.elapsed_time(b) for a, b in zip(ev_s, ev_e)]
     step_ev_ms = float(np.mean(per_step))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, Z, rank, world)
     halo = None
     if world > 1:
-        halo = halo_breakdown(args, pipe, X_loc, Z, de, g_step, dev)
-        kern_ms = halo["spmm_only_ms"]
+        # the aggregation alone takes runs of its own (--full); a plain run's roofline is the whole
+        # pipelined step, exchange included
+        if args.full:
+            halo = halo_breakdown(args, pipe, X_loc, Z, de, g_step, dev)
+        kern_ms = halo["spmm_only_ms"] if halo is not None else step_ev_ms
         tt = torch.tensor([wall, kern_ms, step_ev_ms], dtype=torch.float64,
                           device=dev if args.dist_backend == "nccl" else "cpu")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -398,7 +429,7 @@ def main():
                       "no PMC record for this workload: traffic unmeasured"),
                      "kernel_ms": kern_ms, "kernel_ms_min_max": [min(per_step), max(per_step)] if world == 1 else None,
                      "launches": {"timed": args.steps, "warmup": args.warmup,
-                                  "other": 5 if wname.startswith("C3") else 0,
+                                  "other": 5 if args.full and wname.startswith("C3") else 0,
                                   "note": "warmup + timed launches of this kernel, plus `other` launches of it for "
                                           "dropedge_train_p0.3's forward (p=0.3, fewer bytes, faster): a rocprofv3 "
                                           "average over the process reads that much lower"}
@@ -416,6 +447,12 @@ def main():
     if args.graph == "rmat":
         out["config"]["split"] = graph.split_stats()
         out["config"]["max_row_edges"] = int((graph.rowptr[L::L] - graph.rowptr[:-1:L]).max())
+    if world > 1 and halo is None:
+        out["roofline"]["kernel_ms_basis"] = ("the whole pipelined step, halo exchange included; --full times the "
+                                              "aggregation alone (halo.spmm_only_ms) and computes achieved from it")
+    if not args.full:  # a plain run ends here: the headline line and nothing else
+        finish(out, rank, world)
+        return
     if rank == 0 and args.cpu_seconds > 0:
         if world == 1:
             out["cpu_baseline"], out["parity"] = cpu_baseline(args, g_step, X_loc, Z, L, F)
@@ -441,11 +478,31 @@ def main():
         surface("extras model_one_graph_100k", dev)
         out["extras"]["model_dense_A_mid_n"] = model_mid_extras(dev)
         surface("extras model_dense_A_mid_n", dev)
+    finish(out, rank, world)
+
+
+def finish(out, rank, world):
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def dump_outputs(path, Z, rank, world):
+    """--dump-outputs: what a caller of the timed path holds after the last
+    timed step -- this rank's Z (rows x (L + 1) F, fp32) -- as one float32
+    .npy per rank.  A Z above the rank's share of 32 MiB is cut to a fixed
+    sample of whole rows (numpy default_rng(0), sorted, without repetition):
+    the same rows in every run of the same arguments."""
+    os.makedirs(path, exist_ok=True)
+    rows, row_bytes = Z.shape[0], Z.shape[1] * 4
+    keep = max(1, ((32 << 20) // world) // row_bytes)
+    if rows > keep:
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        Z = Z[torch.from_numpy(idx).to(Z.device)]
+    name = "Z" if world == 1 else f"Z_rank{rank}"
+    np.save(os.path.join(path, name + ".npy"), Z.detach().cpu().numpy().astype(np.float32, copy=False))
 
 
 def halo_breakdown(args, pipe, X_loc, Z, de, g_step, dev, iters=None):

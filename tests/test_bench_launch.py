@@ -40,6 +40,20 @@ def test_gpus_must_be_positive():
     assert r.returncode != 0 and "--gpus must be >= 1" in r.stderr
 
 
+def test_extras_belong_to_a_full_run():
+    """--extras and --c4-reference add to a --full run; on a plain run they
+    are refused at once rather than ignored."""
+    for flag in ("--extras", "--c4-reference"):
+        r = _bench([flag])
+        assert r.returncode != 0 and "--full" in r.stderr
+        assert not any(ln.startswith("{") for ln in r.stdout.splitlines())
+
+
+def test_steps_must_be_positive():
+    r = _bench(["--steps", "0"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+
+
 def test_pmc_traffic_is_keyed_by_workload_world_and_kernel():
     """roofline.traffic comes only from a PMC record of the same workload, at
     the same world size and shard shape, on the same kernel family: the C3

@@ -199,7 +199,7 @@ def _bench_two_ranks(extra, nproc=2):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc),
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", str(nproc),
-           "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0"] + extra
+           "--dist-backend", "gloo", "--steps", "2", "--warmup", "1", "--full", "--cpu-seconds", "0"] + extra
     r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -30,11 +30,11 @@ for step in "$@"; do
   case $step in
     tests) run pytest_gpu 900 python -u -m pytest tests -m gpu -q -rf --timeout 300 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 600 python bench.py ;;
-    bench_extras) run bench_extras 600 python bench.py --extras --cpu-seconds 0 ;;
+    bench) run bench 600 python bench.py --full ;;
+    bench_extras) run bench_extras 600 python bench.py --full --extras --cpu-seconds 0 ;;
     bench_drop) run bench_drop 600 python bench.py --p 0.3 --cpu-seconds 0 ;;
-    bench_c5) run bench_c5 900 python bench.py --workload C5 --steps 5 --warmup 2 ;;
-    bench_c5s) run bench_c5s 600 python bench.py --graph rmat --nodes-per-gpu 1048576 --avg-deg 64 --dim 512 \
+    bench_c5) run bench_c5 900 python bench.py --full --workload C5 --steps 5 --warmup 2 ;;
+    bench_c5s) run bench_c5s 600 python bench.py --full --graph rmat --nodes-per-gpu 1048576 --avg-deg 64 --dim 512 \
                   --p 0.2 --steps 10 --warmup 3 ;;
     prof_bench) run prof_bench 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof_bench" -o run --output-format csv \
                   -- python bench.py ;;
@@ -101,7 +101,7 @@ for step in "$@"; do
     probe_cumask) run probe_cumask 400 python tools/probe_cumask.py ;;
     tests_relabel) run pytest_gpu_relabel 300 python -u -m pytest tests/test_gpu_relabel.py -m gpu -v -rf \
                   --timeout 240 --timeout-method thread ;;
-    bench_c5full) run bench_c5full 900 python bench.py --workload C5 --steps 5 --warmup 2 ;;
+    bench_c5full) run bench_c5full 900 python bench.py --full --workload C5 --steps 5 --warmup 2 ;;
     pmc_c5_fetch2) run pmc_c5_fetch2 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d "$OUT/pmc_c5_fetch2" -o run \
                   --output-format csv -- python bench.py --workload C5 --only fwd --steps 3 --warmup 1 ;;
     pmc_c5_write) run pmc_c5_write 600 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d "$OUT/pmc_c5_write" -o run \
@@ -172,7 +172,7 @@ for step in "$@"; do
                   SQ_BUSY_CU_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA --kernel-trace -d "$OUT/pmc_roles_$n" -o run \
                   --output-format csv -- python tools/probe_wide.py; done ;;
     rehearse_p2) run rehearse_p2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-                  --master-addr 127.0.0.1 --master-port 29613 bench.py --gpus 2 --dist-backend gloo --steps 3 \
+                  --master-addr 127.0.0.1 --master-port 29613 bench.py --gpus 2 --dist-backend gloo --steps 3 --full \
                   --warmup 1 --cpu-seconds 5 ;;
     ab_fused) rm -f gpurun_out/ab_fused_lib.log; run ab_fused 900 tools/ab_fused_lib.sh ${AB_LIBS} ;;
     ab_attn_opt) rm -f gpurun_out/ab_attn_opt.log; run ab_attn_opt 900 tools/ab_attn_opt.sh ${AB_OPTS} ;;
