@@ -24,6 +24,7 @@
 //   dk <= 16 with a workspace: kernel A's dQ is folded into kernel B's dK
 //   pass instead (attn_bwd_kq_x6_kernel: per-workgroup slabs, ordered sum)
 #include "grl_internal.h"
+#include "x6.h"
 
 #include <math.h>
 
@@ -33,8 +34,6 @@
 
 namespace grl {
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 struct AttnArgs {
   const float* Q;      // [B, N, dk]
@@ -444,47 +443,11 @@ __global__ __launch_bounds__(256) void attn_bwd_kv_kernel(AttnArgs a) {
 // columns (features) from per-lane row addresses.  H plane rows keep column c
 // at c ^ ((key & 3) << 5) so the four keys of a transposed read sit in
 // different banks (DV >= 128).
-typedef __bf16 abf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 abf16x2_t __attribute__((ext_vector_type(2)));
-typedef float af32x2_t __attribute__((ext_vector_type(2)));
-typedef short ai16x4_t __attribute__((ext_vector_type(4)));
-typedef short ai16x8_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ uint32_t apack(float a, float b) {
-  af32x2_t p = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(p, abf16x2_t));
-}
-__device__ __forceinline__ float alo(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float ahi(uint32_t u) { return __uint_as_float(u & 0xFFFF0000u); }
-
-// v (4 floats) -> three planes of 4 bf16 with v == p0 + p1 + p2 exactly
-__device__ __forceinline__ void asplit3(float4 v, uint2& p0, uint2& p1, uint2& p2) {
-  p0.x = apack(v.x, v.y);
-  p0.y = apack(v.z, v.w);
-  float4 r = make_float4(v.x - alo(p0.x), v.y - ahi(p0.x), v.z - alo(p0.y), v.w - ahi(p0.y));
-  p1.x = apack(r.x, r.y);
-  p1.y = apack(r.z, r.w);
-  r = make_float4(r.x - alo(p1.x), r.y - ahi(p1.x), r.z - alo(p1.y), r.w - ahi(p1.y));
-  p2.x = apack(r.x, r.y);
-  p2.y = apack(r.z, r.w);
-}
-
-// 8 floats -> three bf16x8 planes
-__device__ __forceinline__ void asplit8(float4 lo, float4 hi, abf16x8_t& a0, abf16x8_t& a1, abf16x8_t& a2) {
-  uint2 l0, l1, l2, h0, h1, h2;
-  asplit3(lo, l0, l1, l2);
-  asplit3(hi, h0, h1, h2);
-  a0 = __builtin_bit_cast(abf16x8_t, make_uint4(l0.x, l0.y, h0.x, h0.y));
-  a1 = __builtin_bit_cast(abf16x8_t, make_uint4(l1.x, l1.y, h1.x, h1.y));
-  a2 = __builtin_bit_cast(abf16x8_t, make_uint4(l2.x, l2.y, h2.x, h2.y));
-}
-
 #if defined(GRL_DIAG) && defined(GRL_ATTN_WI16)
 // what-if (diagnostic builds only; timing, wrong results): every 32x32x16
 // product as two v_mfma_f32_16x16x32_bf16 on the same operand registers into
 // two quarters of the accumulator -- the same FLOPs and pipe cycles in the
 // 16x16x32 shape, to price its clock against the 32x32x16 kernels
-typedef float af32x4_t __attribute__((ext_vector_type(4)));
 #define WI16(q0, q1, a, b)                                                   \
   do {                                                                      \
     q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, q0, 0, 0, 0);        \
@@ -492,8 +455,8 @@ typedef float af32x4_t __attribute__((ext_vector_type(4)));
   } while (0)
 #define MFMA6(acc, a0, a1, a2, b0, b1, b2)                                  \
   do {                                                                      \
-    af32x4_t q0_ = {acc[0], acc[1], acc[2], acc[3]}, q1_ = {acc[4], acc[5], acc[6], acc[7]};       \
-    af32x4_t q2_ = {acc[8], acc[9], acc[10], acc[11]}, q3_ = {acc[12], acc[13], acc[14], acc[15]}; \
+    f32x4_t q0_ = {acc[0], acc[1], acc[2], acc[3]}, q1_ = {acc[4], acc[5], acc[6], acc[7]};       \
+    f32x4_t q2_ = {acc[8], acc[9], acc[10], acc[11]}, q3_ = {acc[12], acc[13], acc[14], acc[15]}; \
     WI16(q0_, q1_, a2, b0);                                                 \
     WI16(q2_, q3_, a1, b1);                                                 \
     WI16(q0_, q1_, a0, b2);                                                 \
@@ -508,15 +471,7 @@ typedef float af32x4_t __attribute__((ext_vector_type(4)));
     }                                                                       \
   } while (0)
 #else
-#define MFMA6(acc, a0, a1, a2, b0, b1, b2)                                  \
-  do {                                                                      \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2, b0, acc, 0, 0, 0);   \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b1, acc, 0, 0, 0);   \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b2, acc, 0, 0, 0);   \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b0, acc, 0, 0, 0);   \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b1, acc, 0, 0, 0);   \
-    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b0, acc, 0, 0, 0);   \
-  } while (0)
+#define MFMA6(acc, a0, a1, a2, b0, b1, b2) x6_mfma(acc, a0, a1, a2, b0, b1, b2)
 #endif
 
 template <int W>
@@ -541,6 +496,14 @@ __device__ __forceinline__ int plane_off(int r, int c) {
   return r * LW + c;
 }
 
+// The column of row r that sits at position pos of a W-wide LAYOUT plane row
+// (the swizzles are involutions): what an LDS-DMA lane landing there fetches.
+template <int W, int LAYOUT>
+__device__ __forceinline__ int plane_src_col(int r, int pos) {
+  static_assert(LAYOUT != PL_SWZ128 || W == 128, "SWZ128 planes are 128 wide");
+  return plane_off<W, W, LAYOUT>(r, pos) - r * W;
+}
+
 // One operand's 32-row blocks -> three bf16 LDS planes of LW-element rows,
 // for the kernels' no-workspace path: fp32 rows are fetched (float4, zero
 // fill) into registers and split at store.  fetch() is issued for the next
@@ -561,7 +524,7 @@ struct XStage {
       if (idx < Stager<W, W>::NF4) {
         const int r = idx / (W / 4), c = (idx % (W / 4)) * 4;
         uint2 p0, p1, p2;
-        asplit3(f32.reg[it], p0, p1, p2);
+        split3(f32.reg[it], p0, p1, p2);
         const int off = plane_off<W, LW, LAYOUT>(r, c);
         *reinterpret_cast<uint2*>(&lds[off]) = p0;
         *reinterpret_cast<uint2*>(&lds[PL + off]) = p1;
@@ -583,27 +546,11 @@ __global__ void attn_split_rows_kernel(const float* __restrict__ src, int64_t ro
 #pragma unroll
     for (int e = 0; e < 4; ++e) v[e] = c + e < width ? src[r * width + c + e] : 0.0f;
     uint2 p0, p1, p2;
-    asplit3(make_float4(v[0], v[1], v[2], v[3]), p0, p1, p2);
+    split3(make_float4(v[0], v[1], v[2], v[3]), p0, p1, p2);
     *reinterpret_cast<uint2*>(planes + r * W + c) = p0;
     *reinterpret_cast<uint2*>(planes + ps + r * W + c) = p1;
     *reinterpret_cast<uint2*>(planes + 2 * ps + r * W + c) = p2;
   }
-}
-
-// global -> LDS DMA of one 16 B chunk per lane (lane l lands at lds_base + 16 l),
-// issued from asm so that hipcc's waitcnt pass neither sees nor waits on it
-__device__ __forceinline__ void adma16(const void* src, const void* lds_base) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(lds_base));
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(dst)
-      : "memory");
 }
 
 // PRE staging: one 32-row block of pre-split planes [3][rows][W] -> LDS
@@ -623,11 +570,9 @@ __device__ __forceinline__ void dma_block(const uint16_t* planes, int64_t ps, in
     if (i < NI) {
       const int e = i * 512 + ln * 8;
       const int pl = e / PL, rem = e % PL, r = rem / W, pos = rem % W;
-      int c = pos;
-      if (LAYOUT == PL_HSWZ && W >= 128) c = pos ^ ((r & 3) << 5);
-      if (LAYOUT == PL_SWZ128) c = ((pos >> 3) ^ (((r & 3) << 2) | ((r >> 2) & 3))) << 3;
+      const int c = plane_src_col<W, LAYOUT>(r, pos);
       const int64_t row = min<int64_t>(r0 + r, N - 1);
-      adma16(planes + pl * ps + row * W + c, lds + i * 512);
+      dma16(planes + pl * ps + row * W + c, lds + i * 512);
     }
   }
 }
@@ -649,9 +594,7 @@ struct DmaRows {
       const int i = wave + NW * j;
       const int e = (i < NI ? i : 0) * 512 + lane * 8;
       const int pl = e / PL, rem = e % PL, r = rem / W, pos = rem % W;
-      int c = pos;
-      if (LAYOUT == PL_HSWZ && W >= 128) c = pos ^ ((r & 3) << 5);
-      if (LAYOUT == PL_SWZ128) c = ((pos >> 3) ^ (((r & 3) << 2) | ((r >> 2) & 3))) << 3;
+      const int c = plane_src_col<W, LAYOUT>(r, pos);
       src[j] = planes_ + pl * ps_ + (int64_t)r * W + c;
     }
   }
@@ -660,7 +603,7 @@ struct DmaRows {
 #pragma unroll
       for (int j = 0; j < NJ; ++j) {
         const int i = wave + NW * j;
-        if (i < NI) adma16(src[j] + r0 * W, lds + i * 512);
+        if (i < NI) dma16(src[j] + r0 * W, lds + i * 512);
       }
     } else {
       dma_block<W, LAYOUT, NW>(planes, ps, r0, N, lds, wave, lane);
@@ -684,7 +627,7 @@ __global__ __launch_bounds__(256) void attn_fwd_x6_kernel(AttnArgs a) {
   const int64_t k_lo = SPLIT ? (int64_t)blockIdx.z * a.kr : 0, k_hi = SPLIT ? min<int64_t>(N, k_lo + a.kr) : N;
 
   // this lane's query, dims kc*16 + 8h + 0..7, split into three planes
-  abf16x8_t qp[KC][3];
+  bf16x8_t qp[KC][3];
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
     float v[8];
@@ -693,7 +636,7 @@ __global__ __launch_bounds__(256) void attn_fwd_x6_kernel(AttnArgs a) {
       const int d = kc * 16 + 8 * h + j;
       v[j] = (q < a.q1 && d < a.dk) ? Qb[q * a.dk + d] * ALOG2E : 0.0f;  // base-2 scores
     }
-    asplit8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), qp[kc][0], qp[kc][1],
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), qp[kc][0], qp[kc][1],
             qp[kc][2]);
   }
   f32x16 o[NT];
@@ -748,9 +691,9 @@ __global__ __launch_bounds__(256) void attn_fwd_x6_kernel(AttnArgs a) {
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int off = l32 * DKP + kc * 16 + 8 * h;
-      const abf16x8_t k0p = *reinterpret_cast<const abf16x8_t*>(&Kp[off]);
-      const abf16x8_t k1p = *reinterpret_cast<const abf16x8_t*>(&Kp[KPL + off]);
-      const abf16x8_t k2p = *reinterpret_cast<const abf16x8_t*>(&Kp[2 * KPL + off]);
+      const bf16x8_t k0p = *reinterpret_cast<const bf16x8_t*>(&Kp[off]);
+      const bf16x8_t k1p = *reinterpret_cast<const bf16x8_t*>(&Kp[KPL + off]);
+      const bf16x8_t k2p = *reinterpret_cast<const bf16x8_t*>(&Kp[2 * KPL + off]);
       MFMA6(s, k0p, k1p, k2p, qp[kc][0], qp[kc][1], qp[kc][2]);
     }
     if (k0 + 32 > k_hi) {  // the last, partial key block only (wave-uniform)
@@ -773,10 +716,10 @@ __global__ __launch_bounds__(256) void attn_fwd_x6_kernel(AttnArgs a) {
     ps += __shfl_xor(ps, 32);
     l = l * alpha + ps;
     m = mn;
-    abf16x8_t pp[2][3];
+    bf16x8_t pp[2][3];
 #pragma unroll
     for (int u = 0; u < 2; ++u)
-      asplit8(make_float4(s[8 * u], s[8 * u + 1], s[8 * u + 2], s[8 * u + 3]),
+      split8(make_float4(s[8 * u], s[8 * u + 1], s[8 * u + 2], s[8 * u + 3]),
               make_float4(s[8 * u + 4], s[8 * u + 5], s[8 * u + 6], s[8 * u + 7]), pp[u][0], pp[u][1], pp[u][2]);
     // the running max of a wave's 32 queries rarely moves after the first
     // key blocks: alpha == 1 exactly then, and the 16 x NT rescale multiplies
@@ -790,17 +733,11 @@ __global__ __launch_bounds__(256) void attn_fwd_x6_kernel(AttnArgs a) {
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        abf16x8_t hp[3];
+        bf16x8_t hp[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
-          typedef __attribute__((address_space(3))) ai16x4_t lds_v4;
           const int key0 = kappa(8 * u + trq, h), key1 = kappa(8 * u + 4 + trq, h);
-          const uint16_t* p0 = &Hp[pl * HPL + hswz<DV>(key0, t * 32 + trc)];
-          const uint16_t* p1 = &Hp[pl * HPL + hswz<DV>(key1, t * 32 + trc)];
-          const ai16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(uintptr_t)(uint32_t)(uintptr_t)p0);
-          const ai16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(uintptr_t)(uint32_t)(uintptr_t)p1);
-          const ai16x8_t v = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-          hp[pl] = __builtin_bit_cast(abf16x8_t, v);
+          hp[pl] = tr8(&Hp[pl * HPL + hswz<DV>(key0, t * 32 + trc)], &Hp[pl * HPL + hswz<DV>(key1, t * 32 + trc)]);
         }
         MFMA6(o[t], hp[0], hp[1], hp[2], pp[u][0], pp[u][1], pp[u][2]);
       }
@@ -858,7 +795,6 @@ __global__ __launch_bounds__(256) void attn_fwd_x6_kernel(AttnArgs a) {
 #ifndef GRL_ATTN_HU2
 #define GRL_ATTN_HU2 1
 #endif
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
 #ifndef GRL_ATTN_PIN_PN
 #define GRL_ATTN_PIN_PN 1
 #endif
@@ -890,7 +826,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
   const int nblk = (int)((k_hi - k_lo + 31) >> 5);
   const bool partial = ((k_hi - k_lo) & 31) != 0;
 
-  abf16x8_t qp[KC][3];
+  bf16x8_t qp[KC][3];
 #pragma unroll
   for (int kc = 0; kc < KC; ++kc) {
     float v[8];
@@ -899,7 +835,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
       const int d = kc * 16 + 8 * h + j;
       v[j] = (q < a.q1 && d < a.dk) ? Qb[q * a.dk + d] * ALOG2E : 0.0f;  // base-2 scores
     }
-    asplit8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), qp[kc][0], qp[kc][1],
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), qp[kc][0], qp[kc][1],
             qp[kc][2]);
   }
   f32x16 o[NT];
@@ -925,15 +861,15 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int off = l32 * DKP + kc * 16 + 8 * h;
-      const abf16x8_t k0p = *reinterpret_cast<const abf16x8_t*>(&Kp[off]);
-      const abf16x8_t k1p = *reinterpret_cast<const abf16x8_t*>(&Kp[KPL + off]);
-      const abf16x8_t k2p = *reinterpret_cast<const abf16x8_t*>(&Kp[2 * KPL + off]);
+      const bf16x8_t k0p = *reinterpret_cast<const bf16x8_t*>(&Kp[off]);
+      const bf16x8_t k1p = *reinterpret_cast<const bf16x8_t*>(&Kp[KPL + off]);
+      const bf16x8_t k2p = *reinterpret_cast<const bf16x8_t*>(&Kp[2 * KPL + off]);
       MFMA6(sc, k0p, k1p, k2p, qp[kc][0], qp[kc][1], qp[kc][2]);
     }
     return sc;
   };
   // online softmax of one block: updates m, l; P -> planes; returns alpha
-  auto softmax = [&](f32x16& sc, abf16x8_t (&pp)[2][3]) {
+  auto softmax = [&](f32x16& sc, bf16x8_t (&pp)[2][3]) {
     float mx = fmaxf(sc[0], sc[1]);
 #pragma unroll
     for (int r = 2; r < 16; r += 2) mx = fmaxf(fmaxf(mx, sc[r]), sc[r + 1]);
@@ -951,7 +887,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
     m = mn;
 #pragma unroll
     for (int u = 0; u < 2; ++u)
-      asplit8(make_float4(sc[8 * u], sc[8 * u + 1], sc[8 * u + 2], sc[8 * u + 3]),
+      split8(make_float4(sc[8 * u], sc[8 * u + 1], sc[8 * u + 2], sc[8 * u + 3]),
               make_float4(sc[8 * u + 4], sc[8 * u + 5], sc[8 * u + 6], sc[8 * u + 7]), pp[u][0], pp[u][1],
               pp[u][2]);
     return alpha;
@@ -962,22 +898,16 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
       if (k0 + kappa(r, h) >= k_hi) sc[r] = -INFINITY;
   };
   // O^T += H^T P^T of the block staged at Hp
-  auto pv = [&](const uint16_t* Hp, const abf16x8_t (&pp)[2][3]) {
+  auto pv = [&](const uint16_t* Hp, const bf16x8_t (&pp)[2][3]) {
 #pragma unroll
     for (int t = 0; t < NT; ++t)
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        abf16x8_t hp[3];
+        bf16x8_t hp[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) {
-          typedef __attribute__((address_space(3))) ai16x4_t lds_v4;
           const int key0 = kappa(8 * u + trq, h), key1 = kappa(8 * u + 4 + trq, h);
-          const uint16_t* p0 = &Hp[pl * HPL + hswz<DV>(key0, t * 32 + trc)];
-          const uint16_t* p1 = &Hp[pl * HPL + hswz<DV>(key1, t * 32 + trc)];
-          const ai16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(uintptr_t)(uint32_t)(uintptr_t)p0);
-          const ai16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(uintptr_t)(uint32_t)(uintptr_t)p1);
-          const ai16x8_t v = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-          hp[pl] = __builtin_bit_cast(abf16x8_t, v);
+          hp[pl] = tr8(&Hp[pl * HPL + hswz<DV>(key0, t * 32 + trc)], &Hp[pl * HPL + hswz<DV>(key1, t * 32 + trc)]);
         }
         MFMA6(o[t], hp[0], hp[1], hp[2], pp[u][0], pp[u][1], pp[u][2]);
       }
@@ -994,7 +924,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
   // prologue: block 0's scores and softmax (o is zero: no rescale)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
-  abf16x8_t pp[2][3];
+  bf16x8_t pp[2][3];
   {
     f32x16 sc = scores(Kp_s);
     if (nblk == 1 && partial) mask(sc, k_lo);
@@ -1031,7 +961,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
     rescale(alpha);
     f32x16 sc = scores(Kp_s + (B2 && HS >= 0 ? (HS + 1) & 3 : kstage(it + 1)) * KST);
     if constexpr (MASK) mask(sc, k0 + 32);
-    abf16x8_t pn[2][3];
+    bf16x8_t pn[2][3];
     // block it's P.H in 2 NT groups of 6 MFMAs; block it+1's softmax cut into
     // 7 pieces placed after groups 1 .. 2 NT - 1 (group 0 covers the score
     // MFMAs' latency), each group fenced so its VALU fills that group's gaps
@@ -1060,41 +990,35 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
         const int u = (pc - 3) >> 1, half = (pc - 3) & 1;
         if (half == 0) {
           uint2 l0, l1, l2;
-          asplit3(make_float4(sc[8 * u], sc[8 * u + 1], sc[8 * u + 2], sc[8 * u + 3]), l0, l1, l2);
-          pn[u][0] = __builtin_bit_cast(abf16x8_t, make_uint4(l0.x, l0.y, 0u, 0u));
-          pn[u][1] = __builtin_bit_cast(abf16x8_t, make_uint4(l1.x, l1.y, 0u, 0u));
-          pn[u][2] = __builtin_bit_cast(abf16x8_t, make_uint4(l2.x, l2.y, 0u, 0u));
+          split3(make_float4(sc[8 * u], sc[8 * u + 1], sc[8 * u + 2], sc[8 * u + 3]), l0, l1, l2);
+          pn[u][0] = __builtin_bit_cast(bf16x8_t, make_uint4(l0.x, l0.y, 0u, 0u));
+          pn[u][1] = __builtin_bit_cast(bf16x8_t, make_uint4(l1.x, l1.y, 0u, 0u));
+          pn[u][2] = __builtin_bit_cast(bf16x8_t, make_uint4(l2.x, l2.y, 0u, 0u));
         } else {
           uint2 h0, h1, h2;
-          asplit3(make_float4(sc[8 * u + 4], sc[8 * u + 5], sc[8 * u + 6], sc[8 * u + 7]), h0, h1, h2);
+          split3(make_float4(sc[8 * u + 4], sc[8 * u + 5], sc[8 * u + 6], sc[8 * u + 7]), h0, h1, h2);
           uint4 w0 = __builtin_bit_cast(uint4, pn[u][0]), w1 = __builtin_bit_cast(uint4, pn[u][1]),
                 w2 = __builtin_bit_cast(uint4, pn[u][2]);
-          pn[u][0] = __builtin_bit_cast(abf16x8_t, make_uint4(w0.x, w0.y, h0.x, h0.y));
-          pn[u][1] = __builtin_bit_cast(abf16x8_t, make_uint4(w1.x, w1.y, h1.x, h1.y));
-          pn[u][2] = __builtin_bit_cast(abf16x8_t, make_uint4(w2.x, w2.y, h2.x, h2.y));
+          pn[u][0] = __builtin_bit_cast(bf16x8_t, make_uint4(w0.x, w0.y, h0.x, h0.y));
+          pn[u][1] = __builtin_bit_cast(bf16x8_t, make_uint4(w1.x, w1.y, h1.x, h1.y));
+          pn[u][2] = __builtin_bit_cast(bf16x8_t, make_uint4(w2.x, w2.y, h2.x, h2.y));
         }
       }
     };
     // group g's H fragments (three planes, transposed reads)
-    auto load_h = [&](int g, abf16x8_t (&hp)[3]) {
+    auto load_h = [&](int g, bf16x8_t (&hp)[3]) {
       const int t = g >> 1, u = g & 1;
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) {
-        typedef __attribute__((address_space(3))) ai16x4_t lds_v4;
         const int key0 = kappa(8 * u + trq, h), key1 = kappa(8 * u + 4 + trq, h);
-        const lds_u16* p0 = Hp + pl * HPL + hswz<DV>(key0, t * 32 + trc);
-        const lds_u16* p1 = Hp + pl * HPL + hswz<DV>(key1, t * 32 + trc);
-        const ai16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)p0);
-        const ai16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)p1);
-        const ai16x8_t v = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-        hp[pl] = __builtin_bit_cast(abf16x8_t, v);
+        hp[pl] = tr8s(Hp + pl * HPL + hswz<DV>(key0, t * 32 + trc), Hp + pl * HPL + hswz<DV>(key1, t * 32 + trc));
       }
     };
     // HPF: the next group's fragments are read one group ahead (two register
     // sets): behind the fence each group's reads would otherwise expose the LDS
     // latency (where the registers allow: 12 more VGPRs)
     constexpr bool HPF = GRL_ATTN_HPF && NT <= 4 && (DKP <= 16 || NW == 4);
-    abf16x8_t hq[HPF ? 2 : 1][3];
+    bf16x8_t hq[HPF ? 2 : 1][3];
     if constexpr (HPF) load_h(0, hq[0]);
     (void)hq;
 #pragma unroll
@@ -1104,7 +1028,7 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
         if (g + 1 < 2 * NT) load_h(g + 1, hq[(g + 1) & 1]);
         MFMA6(o[t], hq[g & 1][0], hq[g & 1][1], hq[g & 1][2], pp[u][0], pp[u][1], pp[u][2]);
       } else {
-        abf16x8_t hp[3];
+        bf16x8_t hp[3];
         load_h(g, hp);
         MFMA6(o[t], hp[0], hp[1], hp[2], pp[u][0], pp[u][1], pp[u][2]);
       }
@@ -1206,26 +1130,9 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
 // ds_read_b128 row reads and the ds_read_b64_tr_b16 reads of 4 consecutive
 // rows.  The 32-column planes (K, Q; dk padded with zeros) are read
 // transposed over 4 consecutive rows of 64 B: conflict-free as they lie.
-// tr8 on LDS-space pointers: constant offsets fold into the reads' immediates
-__device__ __forceinline__ abf16x8_t tr8s(const lds_u16* p0, const lds_u16* p1) {
-  typedef __attribute__((address_space(3))) ai16x4_t lds_v4;
-  const ai16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)p0);
-  const ai16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)p1);
-  const ai16x8_t v = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-  return __builtin_bit_cast(abf16x8_t, v);
-}
-
-__device__ __forceinline__ abf16x8_t tr8(const uint16_t* p0, const uint16_t* p1) {
-  typedef __attribute__((address_space(3))) ai16x4_t lds_v4;
-  const ai16x4_t x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(uintptr_t)(uint32_t)(uintptr_t)p0);
-  const ai16x4_t x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(uintptr_t)(uint32_t)(uintptr_t)p1);
-  const ai16x8_t v = {x0[0], x0[1], x0[2], x0[3], x1[0], x1[1], x1[2], x1[3]};
-  return __builtin_bit_cast(abf16x8_t, v);
-}
-
 // lane's own 8-value slices v[c*16 + 8h + j] of a row, split into planes
 template <int NC>
-__device__ __forceinline__ void row_planes(const float* row, bool valid, int width, int h, abf16x8_t (&pl)[NC][3],
+__device__ __forceinline__ void row_planes(const float* row, bool valid, int width, int h, bf16x8_t (&pl)[NC][3],
                                            float scale = 1.0f) {
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
@@ -1235,16 +1142,41 @@ __device__ __forceinline__ void row_planes(const float* row, bool valid, int wid
       const int d = c * 16 + 8 * h + j;
       v[j] = (valid && d < width) ? row[d] * scale : 0.0f;
     }
-    asplit8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), pl[c][0], pl[c][1], pl[c][2]);
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), pl[c][0], pl[c][1], pl[c][2]);
   }
 }
 
 // 16 fp32 registers (keys / queries kappa(r, h)) -> the two B operands u = 0, 1
-__device__ __forceinline__ void reg_planes(const f32x16& x, abf16x8_t (&pl)[2][3]) {
+__device__ __forceinline__ void reg_planes(const f32x16& x, bf16x8_t (&pl)[2][3]) {
 #pragma unroll
   for (int u = 0; u < 2; ++u)
-    asplit8(make_float4(x[8 * u], x[8 * u + 1], x[8 * u + 2], x[8 * u + 3]),
+    split8(make_float4(x[8 * u], x[8 * u + 1], x[8 * u + 2], x[8 * u + 3]),
             make_float4(x[8 * u + 4], x[8 * u + 5], x[8 * u + 6], x[8 * u + 7]), pl[u][0], pl[u][1], pl[u][2]);
+}
+
+// query qq of batch b for the key-stationary passes: lse2 = rmax log2(e) +
+// log2(rsum) (+inf, so P = 0, for a padded query) and D
+__device__ __forceinline__ void query_stats(const AttnArgs& a, int64_t b, int64_t qq, int64_t q_hi, float& lse2,
+                                            float& D) {
+  const int64_t N = a.N;
+  const bool v = qq < q_hi;
+  lse2 = v ? fmaf(a.smax[b * N + qq], ALOG2E, alog2(a.ssum[b * N + qq])) : INFINITY;
+  D = v ? a.Drow[b * N + qq] : 0.0f;
+}
+
+// The fused dK / dQ kernels' slab reduction of query block qb: its NW partials
+// src[w][d][RP] (one slot, visible behind a barrier) -> slab[d][npad]; wave w
+// adds queries [4w, 4w + 4) x 16 d in wave order.  Split ranges are whole
+// query blocks, so a block never reaches into another split's rows; past N it
+// writes the padding (zeros: P = 0).
+template <int NW, int RP>
+__device__ __forceinline__ void kq_reduce(const float* src, float* slab, int64_t npad, int64_t qb, int wave,
+                                          int lane) {
+  const int q = 4 * wave + (lane >> 4), d = lane & 15;
+  float x = src[d * RP + q];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) x += src[w * 16 * RP + d * RP + q];
+  slab[d * npad + qb + q] = x;
 }
 
 // query-stationary: dQ^T += K^T dS^T
@@ -1260,7 +1192,7 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_x6_kernel(AttnArgs a) {
   const int64_t q = a.q0 + (int64_t)blockIdx.x * 128 + wave * 32 + l32;
   const bool qv = q < a.q1;
   const int64_t k_lo = SPLIT ? (int64_t)blockIdx.z * a.kr : 0, k_hi = SPLIT ? min<int64_t>(N, k_lo + a.kr) : N;
-  abf16x8_t qp[KC][3], dop[FC][3];
+  bf16x8_t qp[KC][3], dop[FC][3];
   row_planes<KC>(a.Q + (b * N + q) * a.dk, qv, a.dk, h, qp, ALOG2E);  // base-2 scores
   row_planes<FC>(a.dO + (b * N + q) * a.dv, qv, a.dv, h, dop);
   // p = 2^(s - lse2); a padded query gets lse2 = +inf, so p = 0
@@ -1313,18 +1245,18 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_x6_kernel(AttnArgs a) {
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int off = l32o * 32 + kc * 16 + 8 * h;
-      const abf16x8_t k0p = *reinterpret_cast<const abf16x8_t*>(&Kp[off]);
-      const abf16x8_t k1p = *reinterpret_cast<const abf16x8_t*>(&Kp[1024 + off]);
-      const abf16x8_t k2p = *reinterpret_cast<const abf16x8_t*>(&Kp[2048 + off]);
+      const bf16x8_t k0p = *reinterpret_cast<const bf16x8_t*>(&Kp[off]);
+      const bf16x8_t k1p = *reinterpret_cast<const bf16x8_t*>(&Kp[1024 + off]);
+      const bf16x8_t k2p = *reinterpret_cast<const bf16x8_t*>(&Kp[2048 + off]);
       MFMA6(s, k0p, k1p, k2p, qp[kc][0], qp[kc][1], qp[kc][2]);
     }
     f32x16 dp = zero16();  // dP^T[key][query] = sum_f H[key][f] dO[query][f]
 #pragma unroll
     for (int fc = 0; fc < FC; ++fc) {
       const int off = swz128(l32o, fc * 16 + 8 * h);
-      const abf16x8_t h0 = *reinterpret_cast<const abf16x8_t*>(&Hp[off]);
-      const abf16x8_t h1 = *reinterpret_cast<const abf16x8_t*>(&Hp[4096 + off]);
-      const abf16x8_t h2 = *reinterpret_cast<const abf16x8_t*>(&Hp[8192 + off]);
+      const bf16x8_t h0 = *reinterpret_cast<const bf16x8_t*>(&Hp[off]);
+      const bf16x8_t h1 = *reinterpret_cast<const bf16x8_t*>(&Hp[4096 + off]);
+      const bf16x8_t h2 = *reinterpret_cast<const bf16x8_t*>(&Hp[8192 + off]);
       MFMA6(dp, h0, h1, h2, dop[fc][0], dop[fc][1], dop[fc][2]);
     }
 #pragma unroll
@@ -1334,12 +1266,12 @@ __global__ __launch_bounds__(256, 2) void attn_bwd_q_x6_kernel(AttnArgs a) {
       for (int r = 0; r < 16; ++r)
         if (k0 + kappa(r, h) >= k_hi) s[r] = 0.0f;
     }
-    abf16x8_t dsp[2][3];
+    bf16x8_t dsp[2][3];
     reg_planes(s, dsp);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r0 = kappa(8 * u + trqo, h), r1 = kappa(8 * u + 4 + trqo, h);
-      abf16x8_t kt[3];
+      bf16x8_t kt[3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl) kt[pl] = tr8(&Kp[pl * 1024 + r0 * 32 + trco], &Kp[pl * 1024 + r1 * 32 + trco]);
       MFMA6(dq, kt[0], kt[1], kt[2], dsp[u][0], dsp[u][1], dsp[u][2]);
@@ -1373,9 +1305,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_kv_x6_kernel(AttnArg
   const int64_t key = (int64_t)blockIdx.x * (32 * NW) + wave * 32 + l32;
   const bool kv = key < N;
   const int64_t q_lo = SPLIT ? (int64_t)blockIdx.z * a.kr : a.q0, q_hi = SPLIT ? min<int64_t>(N, q_lo + a.kr) : a.q1;
-  abf16x8_t kp[KC][3];
+  bf16x8_t kp[KC][3];
   row_planes<KC>(a.K + (b * N + key) * a.dk, kv, a.dk, h, kp, ALOG2E);  // base-2 scores
-  abf16x8_t hp[WANT_H ? 1 : FC][3];
+  bf16x8_t hp[WANT_H ? 1 : FC][3];
   if (!WANT_H) row_planes<WANT_H ? 1 : FC>(a.H + (b * N + key) * a.dv, kv, a.dv, h, hp);
   f32x16 acc[WANT_H ? 4 : 1];
 #pragma unroll
@@ -1393,13 +1325,7 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_kv_x6_kernel(AttnArg
   const bool vq = vec_ok(Qb, a.dk), vo = vec_ok(dOb, a.dv);
   float pm = 0.0f, pd = 0.0f;
   auto fetch_stats = [&](int64_t q0) {
-    if (tid < 32) {
-      const int64_t qq = q0 + tid;
-      const bool v = qq < q_hi;
-      // lse2 = +inf => P = 0 for padded queries
-      pm = v ? fmaf(a.smax[b * N + qq], ALOG2E, alog2(a.ssum[b * N + qq])) : INFINITY;
-      pd = v ? a.Drow[b * N + qq] : 0.0f;
-    }
+    if (tid < 32) query_stats(a, b, q0 + tid, q_hi, pm, pd);
   };
   // dH (WANT_H) has the VGPR room for precomputed DMA addresses; dK does not
   DmaRows<32, PL_PLAIN, NW> qd;
@@ -1458,9 +1384,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_kv_x6_kernel(AttnArg
 #pragma unroll
     for (int kc = 0; kc < KC; ++kc) {
       const int off = l32 * 32 + kc * 16 + 8 * h;
-      const abf16x8_t q0p = *reinterpret_cast<const abf16x8_t*>(&Qp[off]);
-      const abf16x8_t q1p = *reinterpret_cast<const abf16x8_t*>(&Qp[1024 + off]);
-      const abf16x8_t q2p = *reinterpret_cast<const abf16x8_t*>(&Qp[2048 + off]);
+      const bf16x8_t q0p = *reinterpret_cast<const bf16x8_t*>(&Qp[off]);
+      const bf16x8_t q1p = *reinterpret_cast<const bf16x8_t*>(&Qp[1024 + off]);
+      const bf16x8_t q2p = *reinterpret_cast<const bf16x8_t*>(&Qp[2048 + off]);
       MFMA6(s, q0p, q1p, q2p, kp[kc][0], kp[kc][1], kp[kc][2]);
     }
     if (WANT_H) {
@@ -1469,14 +1395,14 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_kv_x6_kernel(AttnArg
         const int qi = kappa(r, h);
         s[r] = aexp2(s[r] - Ms[qi]);  // P (a padded key's column is never stored)
       }
-      abf16x8_t pp[2][3];
+      bf16x8_t pp[2][3];
       reg_planes(s, pp);
 #pragma unroll
       for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           const int r0 = kappa(8 * u + trq, h), r1 = kappa(8 * u + 4 + trq, h);
-          abf16x8_t ot[3];
+          bf16x8_t ot[3];
 #pragma unroll
           for (int pl = 0; pl < 3; ++pl)
             ot[pl] = tr8s(Op3 + pl * 4096 + swz128(r0, t * 32 + trc), Op3 + pl * 4096 + swz128(r1, t * 32 + trc));
@@ -1487,9 +1413,9 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_kv_x6_kernel(AttnArg
 #pragma unroll
       for (int fc = 0; fc < FC; ++fc) {
         const int off = swz128(l32, fc * 16 + 8 * h);
-        const abf16x8_t o0 = *reinterpret_cast<const abf16x8_t*>(&Op[off]);
-        const abf16x8_t o1 = *reinterpret_cast<const abf16x8_t*>(&Op[4096 + off]);
-        const abf16x8_t o2 = *reinterpret_cast<const abf16x8_t*>(&Op[8192 + off]);
+        const bf16x8_t o0 = *reinterpret_cast<const bf16x8_t*>(&Op[off]);
+        const bf16x8_t o1 = *reinterpret_cast<const bf16x8_t*>(&Op[4096 + off]);
+        const bf16x8_t o2 = *reinterpret_cast<const bf16x8_t*>(&Op[8192 + off]);
         MFMA6(dp, o0, o1, o2, hp[fc][0], hp[fc][1], hp[fc][2]);
       }
 #pragma unroll
@@ -1497,12 +1423,12 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_kv_x6_kernel(AttnArg
         const int qi = kappa(r, h);
         s[r] = aexp2(s[r] - Ms[qi]) * (dp[r] - Ds[qi]);  // dS (a padded key's column is never stored)
       }
-      abf16x8_t dsp[2][3];
+      bf16x8_t dsp[2][3];
       reg_planes(s, dsp);
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int r0 = kappa(8 * u + trq, h), r1 = kappa(8 * u + 4 + trq, h);
-        abf16x8_t qt[3];
+        bf16x8_t qt[3];
 #pragma unroll
         for (int pl = 0; pl < 3; ++pl) qt[pl] = tr8s(Qp3 + pl * 1024 + r0 * 32 + trc, Qp3 + pl * 1024 + r1 * 32 + trc);
         MFMA6(acc[0], qt[0], qt[1], qt[2], dsp[u][0], dsp[u][1], dsp[u][2]);
@@ -1569,7 +1495,6 @@ __global__ __launch_bounds__(64 * NW, 8 / NW) void attn_bwd_kv_x6_kernel(AttnArg
 // The same products as the 32x32x16 kernel with the two plane products of
 // S summed inside one MFMA: results equal within fp32 rounding (tested vs
 // float64).  Staging, stats and the query split are the 32x32x16 kernel's.
-typedef float af32x4_t __attribute__((ext_vector_type(4)));
 #define MFMA16(acc, a, b) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16((a), (b), (acc), 0, 0, 0)
 template <bool SPLIT>
 __global__ __launch_bounds__(512, 1) void attn_bwd_h16_kernel(AttnArgs a) {
@@ -1583,7 +1508,7 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_h16_kernel(AttnArgs a) {
   const int64_t key0 = (int64_t)blockIdx.x * (32 * NW) + wave * 32;  // this wave's 32 keys
   const int64_t q_lo = SPLIT ? (int64_t)blockIdx.z * a.kr : a.q0, q_hi = SPLIT ? min<int64_t>(N, q_lo + a.kr) : a.q1;
   // B operands of S: key 16 kt + c16, k = 8 (g & 1) .. + 7, plane by MFMA m and lane half
-  abf16x8_t kb[2][3];
+  bf16x8_t kb[2][3];
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
     const int64_t key = key0 + 16 * kt + c16;
@@ -1594,17 +1519,17 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_h16_kernel(AttnArgs a) {
       const int d = 8 * (g & 1) + j;
       v[j] = (kv && d < a.dk) ? a.K[(b * N + key) * a.dk + d] * ALOG2E : 0.0f;  // base-2 scores
     }
-    abf16x8_t p0, p1, p2;
-    asplit8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), p0, p1, p2);
+    bf16x8_t p0, p1, p2;
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), p0, p1, p2);
     kb[kt][0] = g < 2 ? p0 : p1;  // [K_hi | K_mid]
     kb[kt][1] = p0;               // [K_hi | K_hi]
     kb[kt][2] = g < 2 ? p1 : p2;  // [K_mid | K_lo]
   }
-  af32x4_t acc[FT][2];
+  f32x4_t acc[FT][2];
 #pragma unroll
   for (int ft = 0; ft < FT; ++ft)
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt) acc[ft][kt] = af32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int kt = 0; kt < 2; ++kt) acc[ft][kt] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
   const int64_t qps = (int64_t)gridDim.y * N * 32, ops = (int64_t)gridDim.y * N * 128;
   DmaRows<32, PL_PLAIN, NW> qd;
   DmaRows<128, PL_SWZ128, NW> od;
@@ -1641,17 +1566,17 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_h16_kernel(AttnArgs a) {
       fetch_stats(q0 + 32);
     }
     // S tiles [qt][kt]: rows (queries 8 g + 4 qt + i) in registers, keys 16 kt + c16 on lanes
-    af32x4_t st[2][2];
+    f32x4_t st[2][2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
       const uint16_t* qr = Qp_s + stg * 3 * 1024 + (qrow0 + 4 * qt) * 32 + qcol;
-      abf16x8_t qa[3];
-      qa[0] = *reinterpret_cast<const abf16x8_t*>(qr + qa0 * 1024);
-      qa[1] = *reinterpret_cast<const abf16x8_t*>(qr + qa1 * 1024);
-      qa[2] = *reinterpret_cast<const abf16x8_t*>(qr + qa2 * 1024);
+      bf16x8_t qa[3];
+      qa[0] = *reinterpret_cast<const bf16x8_t*>(qr + qa0 * 1024);
+      qa[1] = *reinterpret_cast<const bf16x8_t*>(qr + qa1 * 1024);
+      qa[2] = *reinterpret_cast<const bf16x8_t*>(qr + qa2 * 1024);
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
-        af32x4_t sacc = {0.0f, 0.0f, 0.0f, 0.0f};  // small products first, hi.hi last: one rounding at |s|
+        f32x4_t sacc = {0.0f, 0.0f, 0.0f, 0.0f};  // small products first, hi.hi last: one rounding at |s|
         MFMA16(sacc, qa[2], kb[kt][2]);
         MFMA16(sacc, qa[1], kb[kt][1]);
         MFMA16(sacc, qa[0], kb[kt][0]);
@@ -1661,19 +1586,19 @@ __global__ __launch_bounds__(512, 1) void attn_bwd_h16_kernel(AttnArgs a) {
     // P = 2^(s - lse2) for queries 8 g .. 8 g + 7 (a padded key's column is never stored)
     const float4 m0 = *reinterpret_cast<const float4*>(Ms + 8 * g);
     const float4 m1 = *reinterpret_cast<const float4*>(Ms + 8 * g + 4);
-    abf16x8_t pb[2][3];
+    bf16x8_t pb[2][3];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       const float4 lo = make_float4(aexp2(st[0][kt][0] - m0.x), aexp2(st[0][kt][1] - m0.y),
                                     aexp2(st[0][kt][2] - m0.z), aexp2(st[0][kt][3] - m0.w));
       const float4 hi = make_float4(aexp2(st[1][kt][0] - m1.x), aexp2(st[1][kt][1] - m1.y),
                                     aexp2(st[1][kt][2] - m1.z), aexp2(st[1][kt][3] - m1.w));
-      asplit8(lo, hi, pb[kt][0], pb[kt][1], pb[kt][2]);
+      split8(lo, hi, pb[kt][0], pb[kt][1], pb[kt][2]);
     }
     // dH^T[feature][key] += dO^T[feature][query] P[query][key]
 #pragma unroll
     for (int ft = 0; ft < FT; ++ft) {
-      abf16x8_t oa[3];
+      bf16x8_t oa[3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
         oa[pl] = tr8s(Op3 + pl * 4096 + swz128(8 * g + q4, 16 * ft + 4 * p4),
@@ -1759,19 +1684,19 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq_x6_kernel(AttnAr
   const int64_t key = a.k0 + (int64_t)blockIdx.x * KW + wave * 32 + l32;
   const bool kv = key < N;
   const int64_t q_lo = SPLIT ? (int64_t)blockIdx.z * a.kr : a.q0, q_hi = SPLIT ? min<int64_t>(N, q_lo + a.kr) : a.q1;
-  abf16x8_t hp[FC][3];
+  bf16x8_t hp[FC][3];
   row_planes<FC>(a.H + (b * N + key) * a.dv, kv, a.dv, h, hp);
   {  // K rows, natural scale (the scores' B operand, and dQ's; zero for padded keys)
-    abf16x8_t kt[1][3];
+    bf16x8_t kt[1][3];
     row_planes<1>(a.K + (b * N + key) * a.dk, kv, a.dk, h, kt);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl)
-      *reinterpret_cast<abf16x8_t*>(&Kt_s[pl * KW * 16 + (wave * 32 + l32) * 16 + 8 * h]) = kt[0][pl];
+      *reinterpret_cast<bf16x8_t*>(&Kt_s[pl * KW * 16 + (wave * 32 + l32) * 16 + 8 * h]) = kt[0][pl];
   }
   // permutation operand of MFMA u: B[k = 8h + j][n] = 1 iff query kappa(8u + j, h) == n (n = l32),
   // i.e. u == n >> 4 and, in half h == (n >> 2) & 1, slot j == 4 ((n >> 3) & 1) + (n & 3)
   const int perm_u = l32 >> 4;
-  ai16x8_t onehot;
+  i16x8_t onehot;
   {
     const int jj = 4 * ((l32 >> 3) & 1) + (l32 & 3);
     const bool mine = h == ((l32 >> 2) & 1);
@@ -1786,23 +1711,10 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq_x6_kernel(AttnAr
   float* slab = a.qslab + ((int64_t)b * gridDim.x + blockIdx.x) * 16 * npad;  // [d][npad]
   float pm = 0.0f, pd = 0.0f;
   auto fetch_stats = [&](int64_t q0) {
-    if (tid < 32) {
-      const int64_t qq = q0 + tid;
-      const bool v = qq < q_hi;
-      pm = v ? fmaf(a.smax[b * N + qq], ALOG2E, alog2(a.ssum[b * N + qq])) : INFINITY;  // P = 0 when padded
-      pd = v ? a.Drow[b * N + qq] : 0.0f;
-    }
+    if (tid < 32) query_stats(a, b, q0 + tid, q_hi, pm, pd);
   };
-  // block qb's eight partials (its slot, visible behind a barrier): wave w adds queries
-  // [4w, 4w + 4) x 16 d in wave order.  Split ranges are whole query blocks, so a block
-  // never reaches into another split's rows; past N it writes the padding (zeros: P = 0).
   auto reduce = [&](int64_t qb) {
-    const float* src = Red_s + (int)(((qb - q_lo) >> 5) & 1) * RSLOT;
-    const int q = 4 * wave + (lane >> 4), d = lane & 15;
-    float x = src[d * RP + q];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) x += src[w * 16 * RP + d * RP + q];
-    slab[d * npad + qb + q] = x;
+    kq_reduce<NW, RP>(Red_s + (int)(((qb - q_lo) >> 5) & 1) * RSLOT, slab, npad, qb, wave, lane);
   };
   dma_block<16, PL_PLAIN, NW>(Qpb, qps, q_lo, N, Qp_s, wave, lane);
   dma_block<128, PL_SWZ128, NW>(Opb, ops, q_lo, N, Op_s, wave, lane);
@@ -1831,21 +1743,21 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq_x6_kernel(AttnAr
     f32x16 s = zero16();  // natural-scale scores q.k (base 2 applied in the exponent's fma)
     {
       const int off = l32 * 16 + 8 * h, koff = (wave * 32 + l32) * 16 + 8 * h;
-      const abf16x8_t q0p = *reinterpret_cast<const abf16x8_t*>(&Qp[off]);
-      const abf16x8_t q1p = *reinterpret_cast<const abf16x8_t*>(&Qp[512 + off]);
-      const abf16x8_t q2p = *reinterpret_cast<const abf16x8_t*>(&Qp[1024 + off]);
-      const abf16x8_t k0p = *reinterpret_cast<const abf16x8_t*>(&Kt_s[koff]);
-      const abf16x8_t k1p = *reinterpret_cast<const abf16x8_t*>(&Kt_s[KW * 16 + koff]);
-      const abf16x8_t k2p = *reinterpret_cast<const abf16x8_t*>(&Kt_s[2 * KW * 16 + koff]);
+      const bf16x8_t q0p = *reinterpret_cast<const bf16x8_t*>(&Qp[off]);
+      const bf16x8_t q1p = *reinterpret_cast<const bf16x8_t*>(&Qp[512 + off]);
+      const bf16x8_t q2p = *reinterpret_cast<const bf16x8_t*>(&Qp[1024 + off]);
+      const bf16x8_t k0p = *reinterpret_cast<const bf16x8_t*>(&Kt_s[koff]);
+      const bf16x8_t k1p = *reinterpret_cast<const bf16x8_t*>(&Kt_s[KW * 16 + koff]);
+      const bf16x8_t k2p = *reinterpret_cast<const bf16x8_t*>(&Kt_s[2 * KW * 16 + koff]);
       MFMA6(s, q0p, q1p, q2p, k0p, k1p, k2p);
     }
     f32x16 dp = zero16();  // dP[query][key] = sum_f dO[query][f] H[key][f]
 #pragma unroll
     for (int fc = 0; fc < FC; ++fc) {
       const int off = swz128(l32, fc * 16 + 8 * h);
-      const abf16x8_t o0 = *reinterpret_cast<const abf16x8_t*>(&Op[off]);
-      const abf16x8_t o1 = *reinterpret_cast<const abf16x8_t*>(&Op[4096 + off]);
-      const abf16x8_t o2 = *reinterpret_cast<const abf16x8_t*>(&Op[8192 + off]);
+      const bf16x8_t o0 = *reinterpret_cast<const bf16x8_t*>(&Op[off]);
+      const bf16x8_t o1 = *reinterpret_cast<const bf16x8_t*>(&Op[4096 + off]);
+      const bf16x8_t o2 = *reinterpret_cast<const bf16x8_t*>(&Op[8192 + off]);
       MFMA6(dp, o0, o1, o2, hp[fc][0], hp[fc][1], hp[fc][2]);
     }
 #pragma unroll
@@ -1853,12 +1765,12 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq_x6_kernel(AttnAr
       const int qi = kappa(r, h);
       s[r] = aexp2(fmaf(s[r], ALOG2E, -Ms[qi])) * (dp[r] - Ds[qi]);  // dS
     }
-    abf16x8_t dsp[2][3];
+    bf16x8_t dsp[2][3];
     reg_planes(s, dsp);
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r0 = kappa(8 * u + trq, h), r1 = kappa(8 * u + 4 + trq, h);
-      abf16x8_t qt[3];
+      bf16x8_t qt[3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
         qt[pl] = tr8(&Qp[pl * 512 + r0 * 16 + (trc & 15)], &Qp[pl * 512 + r1 * 16 + (trc & 15)]);
@@ -1872,43 +1784,43 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq_x6_kernel(AttnAr
     // and not always the same planes (a re-split of hi + mid + lo can round
     // differently), so dQ's last bits differ between the two forms
 #if GRL_ATTN_TPLANES
-    abf16x8_t dtp[2][3];
+    bf16x8_t dtp[2][3];
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl) {
       f32x16 dt = zero16();
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
-        ai16x8_t pv;
+        i16x8_t pv;
 #pragma unroll
         for (int j = 0; j < 8; ++j) pv[j] = u == perm_u ? onehot[j] : (short)0;
-        dt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsp[u][pl], __builtin_bit_cast(abf16x8_t, pv), dt, 0, 0, 0);
+        mfma_bf16(dt, dsp[u][pl], __builtin_bit_cast(bf16x8_t, pv));
       }
 #pragma unroll
       for (int u = 0; u < 2; ++u)
-        dtp[u][pl] = __builtin_bit_cast(abf16x8_t, make_uint4(apack(dt[8 * u], dt[8 * u + 1]),
-                                                              apack(dt[8 * u + 2], dt[8 * u + 3]),
-                                                              apack(dt[8 * u + 4], dt[8 * u + 5]),
-                                                              apack(dt[8 * u + 6], dt[8 * u + 7])));
+        dtp[u][pl] = __builtin_bit_cast(bf16x8_t, make_uint4(pack_bf16(dt[8 * u], dt[8 * u + 1]),
+                                                              pack_bf16(dt[8 * u + 2], dt[8 * u + 3]),
+                                                              pack_bf16(dt[8 * u + 4], dt[8 * u + 5]),
+                                                              pack_bf16(dt[8 * u + 6], dt[8 * u + 7])));
     }
 #else
     f32x16 dt = zero16();
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
-      ai16x8_t pv;
+      i16x8_t pv;
 #pragma unroll
       for (int j = 0; j < 8; ++j) pv[j] = u == perm_u ? onehot[j] : (short)0;
-      const abf16x8_t perm = __builtin_bit_cast(abf16x8_t, pv);
+      const bf16x8_t perm = __builtin_bit_cast(bf16x8_t, pv);
 #pragma unroll
-      for (int pl = 0; pl < 3; ++pl) dt = __builtin_amdgcn_mfma_f32_32x32x16_bf16(dsp[u][pl], perm, dt, 0, 0, 0);
+      for (int pl = 0; pl < 3; ++pl) mfma_bf16(dt, dsp[u][pl], perm);
     }
-    abf16x8_t dtp[2][3];
+    bf16x8_t dtp[2][3];
     reg_planes(dt, dtp);
 #endif
     f32x16 dq = zero16();  // dQ_blk[query][d] over this wave's 32 keys (columns d >= 16 discarded)
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const int r0 = wave * 32 + kappa(8 * u + trq, h), r1 = wave * 32 + kappa(8 * u + 4 + trq, h);
-      abf16x8_t kt[3];
+      bf16x8_t kt[3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
         kt[pl] = tr8(&Kt_s[pl * KW * 16 + r0 * 16 + (trc & 15)], &Kt_s[pl * KW * 16 + r1 * 16 + (trc & 15)]);
@@ -1997,13 +1909,13 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq16_kernel(AttnArg
       const int d = 8 * (lane & 1) + j;
       v[j] = (key < N && d < a.dk) ? a.K[(b * N + key) * a.dk + d] : 0.0f;
     }
-    abf16x8_t p[3];
-    asplit8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), p[0], p[1], p[2]);
+    bf16x8_t p[3];
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), p[0], p[1], p[2]);
 #pragma unroll
     for (int pl = 0; pl < 3; ++pl)
-      *reinterpret_cast<abf16x8_t*>(&Kt_s[pl * KW * 16 + (wave * 32 + (lane >> 1)) * 16 + 8 * (lane & 1)]) = p[pl];
+      *reinterpret_cast<bf16x8_t*>(&Kt_s[pl * KW * 16 + (wave * 32 + (lane >> 1)) * 16 + 8 * (lane & 1)]) = p[pl];
   }
-  abf16x8_t hb[2][FC][3];
+  bf16x8_t hb[2][FC][3];
 #pragma unroll
   for (int kt = 0; kt < 2; ++kt) {
     const int64_t key = key0 + 16 * kt + c16;
@@ -2016,12 +1928,12 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq16_kernel(AttnArg
         const int f = 32 * fc + 8 * g + j;
         v[j] = (kv && f < a.dv) ? a.H[(b * N + key) * a.dv + f] : 0.0f;
       }
-      asplit8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hb[kt][fc][0], hb[kt][fc][1],
+      split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hb[kt][fc][0], hb[kt][fc][1],
               hb[kt][fc][2]);
     }
   }
   // B operand of dQ: K[key 8 g + j][d c16], the key order of the transposed dS
-  abf16x8_t kq[3];
+  bf16x8_t kq[3];
   {
     float v[8];
 #pragma unroll
@@ -2029,9 +1941,9 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq16_kernel(AttnArg
       const int64_t key = key0 + 8 * g + j;
       v[j] = (key < N && c16 < a.dk) ? a.K[(b * N + key) * a.dk + c16] : 0.0f;
     }
-    asplit8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), kq[0], kq[1], kq[2]);
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), kq[0], kq[1], kq[2]);
   }
-  af32x4_t acck[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
+  f32x4_t acck[2] = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}};
   const int64_t qps = (int64_t)gridDim.y * N * 16, ops = (int64_t)gridDim.y * N * 128;
   const uint16_t* Qpb = a.Qpl16 + b * N * 16;
   const uint16_t* Opb = a.Opl + b * N * 128;
@@ -2039,20 +1951,10 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq16_kernel(AttnArg
   float* slab = a.qslab + ((int64_t)b * gridDim.x + blockIdx.x) * 16 * npad;  // [d][npad]
   float pm = 0.0f, pd = 0.0f;
   auto fetch_stats = [&](int64_t q0) {
-    if (tid < 32) {
-      const int64_t qq = q0 + tid;
-      const bool v = qq < q_hi;
-      pm = v ? fmaf(a.smax[b * N + qq], ALOG2E, alog2(a.ssum[b * N + qq])) : INFINITY;  // P = 0 when padded
-      pd = v ? a.Drow[b * N + qq] : 0.0f;
-    }
+    if (tid < 32) query_stats(a, b, q0 + tid, q_hi, pm, pd);
   };
-  auto reduce = [&](int64_t qb) {  // as attn_bwd_kq_x6_kernel: wave w adds queries [4w, 4w + 4) x 16 d
-    const float* src = Red_s + (int)(((qb - q_lo) >> 5) & 1) * RSLOT;
-    const int q = 4 * wave + (lane >> 4), d = lane & 15;
-    float x = src[d * RP + q];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) x += src[w * 16 * RP + d * RP + q];
-    slab[d * npad + qb + q] = x;
+  auto reduce = [&](int64_t qb) {
+    kq_reduce<NW, RP>(Red_s + (int)(((qb - q_lo) >> 5) & 1) * RSLOT, slab, npad, qb, wave, lane);
   };
   dma_block<16, PL_PLAIN, NW>(Qpb, qps, q_lo, N, Qp_s, wave, lane);
   dma_block<128, PL_SWZ128, NW>(Opb, ops, q_lo, N, Op_s, wave, lane);
@@ -2082,23 +1984,23 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq16_kernel(AttnArg
     }
     if (q0 > q_lo) reduce(q0 - 32);
     // S and dP tiles [qt][kt]: rows (queries 8 g + 4 qt + i) in registers, keys 16 kt + c16 on lanes
-    af32x4_t st[2][2], dp[2][2];
+    f32x4_t st[2][2], dp[2][2];
 #pragma unroll
     for (int qt = 0; qt < 2; ++qt) {
       const uint16_t* qr = Qp + (qrow0 + 4 * qt) * 16 + 8 * (g & 1);
-      abf16x8_t qa[3];
-      qa[0] = *reinterpret_cast<const abf16x8_t*>(qr);
-      qa[1] = *reinterpret_cast<const abf16x8_t*>(qr + qa1 * 512);
-      qa[2] = *reinterpret_cast<const abf16x8_t*>(qr + qa2 * 512);
+      bf16x8_t qa[3];
+      qa[0] = *reinterpret_cast<const bf16x8_t*>(qr);
+      qa[1] = *reinterpret_cast<const bf16x8_t*>(qr + qa1 * 512);
+      qa[2] = *reinterpret_cast<const bf16x8_t*>(qr + qa2 * 512);
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         const uint16_t* kr = Kt_s + (wave * 32 + 16 * kt + c16) * 16 + 8 * (g & 1);
-        af32x4_t s = {0.0f, 0.0f, 0.0f, 0.0f};  // small products first, hi.hi last: one rounding at |s|
-        MFMA16(s, qa[2], *reinterpret_cast<const abf16x8_t*>(kr + kb2 * KW * 16));
-        MFMA16(s, qa[1], *reinterpret_cast<const abf16x8_t*>(kr));
-        MFMA16(s, qa[0], *reinterpret_cast<const abf16x8_t*>(kr + kb0 * KW * 16));
+        f32x4_t s = {0.0f, 0.0f, 0.0f, 0.0f};  // small products first, hi.hi last: one rounding at |s|
+        MFMA16(s, qa[2], *reinterpret_cast<const bf16x8_t*>(kr + kb2 * KW * 16));
+        MFMA16(s, qa[1], *reinterpret_cast<const bf16x8_t*>(kr));
+        MFMA16(s, qa[0], *reinterpret_cast<const bf16x8_t*>(kr + kb0 * KW * 16));
         st[qt][kt] = s;
-        dp[qt][kt] = af32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
+        dp[qt][kt] = f32x4_t{0.0f, 0.0f, 0.0f, 0.0f};
       }
     }
 #pragma unroll
@@ -2106,16 +2008,16 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq16_kernel(AttnArg
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
         const int off = swz128(qrow0 + 4 * qt, 32 * fc + 8 * g);  // conflict-free in the b128 lane groups
-        abf16x8_t oa[3];
+        bf16x8_t oa[3];
 #pragma unroll
-        for (int pl = 0; pl < 3; ++pl) oa[pl] = *reinterpret_cast<const abf16x8_t*>(&Op[pl * 4096 + off]);
+        for (int pl = 0; pl < 3; ++pl) oa[pl] = *reinterpret_cast<const bf16x8_t*>(&Op[pl * 4096 + off]);
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) X6_16(dp[qt][kt], oa, hb[kt][fc]);
       }
     // dS = P (dP - D) for queries 8 g .. 8 g + 7, split into planes: dS[q][key] as B (k = q)
     const float4 m0 = *reinterpret_cast<const float4*>(Ms + 8 * g), m1 = *reinterpret_cast<const float4*>(Ms + 8 * g + 4);
     const float4 e0 = *reinterpret_cast<const float4*>(Ds + 8 * g), e1 = *reinterpret_cast<const float4*>(Ds + 8 * g + 4);
-    abf16x8_t dsp[2][3];
+    bf16x8_t dsp[2][3];
 #pragma unroll
     for (int kt = 0; kt < 2; ++kt) {
       const float4 lo = make_float4(aexp2(fmaf(st[0][kt][0], ALOG2E, -m0.x)) * (dp[0][kt][0] - e0.x),
@@ -2126,17 +2028,17 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq16_kernel(AttnArg
                                     aexp2(fmaf(st[1][kt][1], ALOG2E, -m1.y)) * (dp[1][kt][1] - e1.y),
                                     aexp2(fmaf(st[1][kt][2], ALOG2E, -m1.z)) * (dp[1][kt][2] - e1.z),
                                     aexp2(fmaf(st[1][kt][3], ALOG2E, -m1.w)) * (dp[1][kt][3] - e1.w));
-      asplit8(lo, hi, dsp[kt][0], dsp[kt][1], dsp[kt][2]);
+      split8(lo, hi, dsp[kt][0], dsp[kt][1], dsp[kt][2]);
     }
     {  // dK^T[d][key] += Q^T[d][q] dS[q][key]; Q^T rows 8 g .. 8 g + 7 by transposed reads
-      abf16x8_t qT[3];
+      bf16x8_t qT[3];
 #pragma unroll
       for (int pl = 0; pl < 3; ++pl)
         qT[pl] = tr8s(Qt + pl * 512 + (8 * g + q4) * 16 + 4 * p4, Qt + pl * 512 + (8 * g + 4 + q4) * 16 + 4 * p4);
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) X6_16(acck[kt], qT, dsp[kt]);
     }
-    abf16x8_t dt[2][3];
+    bf16x8_t dt[2][3];
     {
       // dS^T through this wave's LDS slots: plane pl's [key][q] rows (16-B chunk c of row k at
       // c ^ ((k >> 2) & 3): conflict-free row writes and transposed reads), read back by
@@ -2148,7 +2050,7 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq16_kernel(AttnArg
 #pragma unroll
         for (int kt = 0; kt < 2; ++kt) {
           const int k = 16 * kt + c16;
-          *reinterpret_cast<abf16x8_t*>(slot + k * 32 + ((g ^ ((k >> 2) & 3)) << 3)) = dsp[kt][pl];
+          *reinterpret_cast<bf16x8_t*>(slot + k * 32 + ((g ^ ((k >> 2) & 3)) << 3)) = dsp[kt][pl];
         }
         const lds_u16* sl = (const lds_u16*)Dt_s + (wave * 2 + (pl & 1)) * 1024;
         const int k0 = 8 * g + q4, k1 = 8 * g + 4 + q4;
@@ -2164,7 +2066,7 @@ __global__ __launch_bounds__(64 * KQ_WAVES, 1) void attn_bwd_kq16_kernel(AttnArg
     float* dst = Red_s + stg * RSLOT + wave * 16 * RP + c16 * RP + 4 * g;
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt) {
-      af32x4_t dq = {0.0f, 0.0f, 0.0f, 0.0f};
+      f32x4_t dq = {0.0f, 0.0f, 0.0f, 0.0f};
       X6_16(dq, dt[nt], kq);
       *reinterpret_cast<float4*>(dst + 16 * nt) = make_float4(dq[0], dq[1], dq[2], dq[3]);
     }
@@ -2281,6 +2183,16 @@ bool attn_kq16_enabled() { return opt(OPT_ATTN_KQ16) != 0; }
 // path option attn_pipe = 0 keeps the unpipelined x6 forward (A/B aid)
 bool attn_pipe_enabled() { return opt(OPT_ATTN_PIPE) != 0; }
 
+// f(std::true_type / std::false_type): a run-time bool as a template argument
+// of the kernel that the generic lambda f launches
+template <class F>
+void with_bool(bool v, F&& f) {
+  if (v)
+    f(std::true_type{});
+  else
+    f(std::false_type{});
+}
+
 template <int DKP, int NT>
 int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t st) {
   AttnArgs a = a0;
@@ -2298,17 +2210,10 @@ int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t
   const bool pre = pass == PASS_BWD_KV ? (a.Qpl && a.Opl) : (a.Kpl && a.Hpl);
   const int64_t rows = B * a.N;
   const unsigned red = (unsigned)std::min<int64_t>(ceil_div(rows * std::max(a.dv, 1), 256), 8192);
-#define GRL_X6L(KERNEL, ...)                                                                      \
-  do {                                                                                              \
-    if (pre && S > 1)                                                                               \
-      hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, true>), grid, dim3(256), 0, st, a);             \
-    else if (pre)                                                                                   \
-      hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true, false>), grid, dim3(256), 0, st, a);            \
-    else if (S > 1)                                                                                 \
-      hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, true>), grid, dim3(256), 0, st, a);            \
-    else                                                                                            \
-      hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false, false>), grid, dim3(256), 0, st, a);           \
-  } while (0)
+  // the PRE (operands pre-split by the caller) and SPLIT (S > 1) template arguments of an x6 kernel
+  auto pre_split = [&](auto launch) {
+    with_bool(pre, [&](auto p) { with_bool(S > 1, [&](auto s) { launch(p, s); }); });
+  };
   if constexpr (DKP > 32) {
     if (pass == PASS_FWD)
       hipLaunchKernelGGL((attn_fwd_kernel<DKP, NT>), grid, dim3(256), 0, st, a);
@@ -2319,17 +2224,17 @@ int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t
   } else if (pass == PASS_FWD && x6) {
     if (pre && attn_pipe_enabled() && attn_fwd8_enabled()) {  // 256 queries per workgroup
       const dim3 g8((unsigned)ceil_div(nq, 256), (unsigned)B, (unsigned)S);
-      if (S > 1)
-        hipLaunchKernelGGL((attn_fwd_x6p_kernel<DKP, NT, true, 8>), g8, dim3(512), 0, st, a);
-      else
-        hipLaunchKernelGGL((attn_fwd_x6p_kernel<DKP, NT, false, 8>), g8, dim3(512), 0, st, a);
+      with_bool(S > 1, [&](auto s) {
+        hipLaunchKernelGGL((attn_fwd_x6p_kernel<DKP, NT, s(), 8>), g8, dim3(512), 0, st, a);
+      });
     } else if (pre && attn_pipe_enabled()) {
-      if (S > 1)
-        hipLaunchKernelGGL((attn_fwd_x6p_kernel<DKP, NT, true>), grid, dim3(256), 0, st, a);
-      else
-        hipLaunchKernelGGL((attn_fwd_x6p_kernel<DKP, NT, false>), grid, dim3(256), 0, st, a);
+      with_bool(S > 1, [&](auto s) {
+        hipLaunchKernelGGL((attn_fwd_x6p_kernel<DKP, NT, s()>), grid, dim3(256), 0, st, a);
+      });
     } else {
-      GRL_X6L(attn_fwd_x6_kernel, DKP, NT);
+      pre_split([&](auto p, auto s) {
+        hipLaunchKernelGGL((attn_fwd_x6_kernel<DKP, NT, p(), s()>), grid, dim3(256), 0, st, a);
+      });
     }
     if (S > 1) {
       GRL_LAUNCH_CHECK();
@@ -2339,7 +2244,9 @@ int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t
     hipLaunchKernelGGL((attn_fwd_kernel<DKP, NT>), grid, dim3(256), 0, st, a);
   } else if (x6) {  // backward x6: dv in (96, 128]
     if (pass == PASS_BWD_Q) {
-      GRL_X6L(attn_bwd_q_x6_kernel, DKP);
+      pre_split([&](auto p, auto s) {
+        hipLaunchKernelGGL((attn_bwd_q_x6_kernel<DKP, p(), s()>), grid, dim3(256), 0, st, a);
+      });
       if (S > 1 && a.dk > 0) {
         GRL_LAUNCH_CHECK();
         hipLaunchKernelGGL(attn_slab_sum_kernel, dim3(red), dim3(256), 0, st, a.part, rows * a.dk, S, a.dQ);
@@ -2348,18 +2255,16 @@ int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t
       if (S > 1) a.part2 = a.part + (int64_t)S * rows * a.dv;
       if (pre && attn_dh8_enabled() && DKP == 16 && attn_dh16_enabled()) {  // dH in 16 x 16 tiles
         const dim3 g8((unsigned)ceil_div(a.N, 256), (unsigned)B, (unsigned)S);
-        if (S > 1)
-          hipLaunchKernelGGL((attn_bwd_h16_kernel<true>), g8, dim3(512), 0, st, a);
-        else
-          hipLaunchKernelGGL((attn_bwd_h16_kernel<false>), g8, dim3(512), 0, st, a);
+        with_bool(S > 1, [&](auto s) { hipLaunchKernelGGL((attn_bwd_h16_kernel<s()>), g8, dim3(512), 0, st, a); });
       } else if (pre && attn_dh8_enabled()) {  // dH on 256-key workgroups
         const dim3 g8((unsigned)ceil_div(a.N, 256), (unsigned)B, (unsigned)S);
-        if (S > 1)
-          hipLaunchKernelGGL((attn_bwd_kv_x6_kernel<DKP, true, true, true, 8>), g8, dim3(512), 0, st, a);
-        else
-          hipLaunchKernelGGL((attn_bwd_kv_x6_kernel<DKP, true, true, false, 8>), g8, dim3(512), 0, st, a);
+        with_bool(S > 1, [&](auto s) {
+          hipLaunchKernelGGL((attn_bwd_kv_x6_kernel<DKP, true, true, s(), 8>), g8, dim3(512), 0, st, a);
+        });
       } else {
-        GRL_X6L(attn_bwd_kv_x6_kernel, DKP, true);
+        pre_split([&](auto p, auto s) {
+          hipLaunchKernelGGL((attn_bwd_kv_x6_kernel<DKP, true, p(), s()>), grid, dim3(256), 0, st, a);
+        });
       }
       GRL_LAUNCH_CHECK();
       bool kq = false;
@@ -2372,14 +2277,14 @@ int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t
             AttnArgs ac = a;
             ac.k0 = x0 * KQ_KEYS;
             const dim3 gkq((unsigned)std::min<int64_t>(xc, xall - x0), (unsigned)B, (unsigned)S);
-            if (attn_kq16_enabled() && S > 1)
-              hipLaunchKernelGGL((attn_bwd_kq16_kernel<true>), gkq, dim3(64 * KQ_WAVES), 0, st, ac);
-            else if (attn_kq16_enabled())
-              hipLaunchKernelGGL((attn_bwd_kq16_kernel<false>), gkq, dim3(64 * KQ_WAVES), 0, st, ac);
-            else if (S > 1)
-              hipLaunchKernelGGL((attn_bwd_kq_x6_kernel<true>), gkq, dim3(64 * KQ_WAVES), 0, st, ac);
+            if (attn_kq16_enabled())
+              with_bool(S > 1, [&](auto s) {
+                hipLaunchKernelGGL((attn_bwd_kq16_kernel<s()>), gkq, dim3(64 * KQ_WAVES), 0, st, ac);
+              });
             else
-              hipLaunchKernelGGL((attn_bwd_kq_x6_kernel<false>), gkq, dim3(64 * KQ_WAVES), 0, st, ac);
+              with_bool(S > 1, [&](auto s) {
+                hipLaunchKernelGGL((attn_bwd_kq_x6_kernel<s()>), gkq, dim3(64 * KQ_WAVES), 0, st, ac);
+              });
             GRL_LAUNCH_CHECK();
             if (a.dk > 0)
               hipLaunchKernelGGL(attn_qslab_sum_kernel,
@@ -2388,7 +2293,10 @@ int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t
           }
         }
       }
-      if (!kq) GRL_X6L(attn_bwd_kv_x6_kernel, DKP, false);
+      if (!kq)
+        pre_split([&](auto p, auto s) {
+          hipLaunchKernelGGL((attn_bwd_kv_x6_kernel<DKP, false, p(), s()>), grid, dim3(256), 0, st, a);
+        });
       if (S > 1) {
         GRL_LAUNCH_CHECK();
         hipLaunchKernelGGL(attn_slab_sum_kernel, dim3(red), dim3(256), 0, st, a.part, rows * a.dv, S, a.dH);
@@ -2398,7 +2306,6 @@ int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t
         }
       }
     }
-#undef GRL_X6L
   } else if (pass == PASS_BWD_Q) {
     hipLaunchKernelGGL((attn_bwd_q_kernel<DKP, NT>), grid, dim3(256), 0, st, a);
   } else {

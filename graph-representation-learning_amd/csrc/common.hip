@@ -40,31 +40,12 @@ struct OptDef {
   const char* name;
   int64_t def, lo, hi;
 };
-constexpr OptDef kOpts[OPT_COUNT] = {
-    {"gemm_x6", 1, 0, 1},
-    {"graphconv_fused", 1, 0, 1},
-    {"graphconv_fused_bwd", 1, 0, 1},
-    {"fg_ws", 1, 0, 1},
-    {"spmm_wide", -1, -1, 1},
-    {"spmm_blocks_per_cu", 24, 1, 64},
-    {"attn_x6", 1, 0, 1},
-    {"attn_fwd8", 1, 0, 1},
-    {"attn_dh8", 1, 0, 1},
-    {"attn_fused_dq", 1, 0, 1},
-    {"attn_pipe", 1, 0, 1},
-    {"attn_dh16", 1, 0, 1},
-    {"attn_kq16", 1, 0, 1},
-    {"attn_qslab_max", 0, 0, INT64_MAX},
-    {"ws_spin", 0, 0, (int64_t)1 << 30},
-    {"ws_status_sync", 0, 0, 1},
-};
-std::atomic<int64_t> g_opt[OPT_COUNT] = {
-    {kOpts[0].def},  {kOpts[1].def},  {kOpts[2].def},  {kOpts[3].def},  {kOpts[4].def},
-    {kOpts[5].def},  {kOpts[6].def},  {kOpts[7].def},  {kOpts[8].def},  {kOpts[9].def},
-    {kOpts[10].def}, {kOpts[11].def}, {kOpts[12].def}, {kOpts[13].def}, {kOpts[14].def},
-    {kOpts[15].def},
-};
-static_assert(OPT_COUNT == 16, "one default per option");
+#define GRL_OPT_DEF(id, name, def, lo, hi) {name, def, lo, hi},
+#define GRL_OPT_INIT(id, name, def, lo, hi) {def},
+constexpr OptDef kOpts[OPT_COUNT] = {GRL_OPTIONS(GRL_OPT_DEF)};
+std::atomic<int64_t> g_opt[OPT_COUNT] = {GRL_OPTIONS(GRL_OPT_INIT)};
+#undef GRL_OPT_DEF
+#undef GRL_OPT_INIT
 
 int find_opt(const char* name) {
   for (int i = 0; name && i < OPT_COUNT; ++i)

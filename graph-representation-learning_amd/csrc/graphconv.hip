@@ -26,6 +26,7 @@
 #include <cstring>
 
 #include "grl_internal.h"
+#include "x6.h"
 
 #include <cstdlib>
 #include <mutex>
@@ -45,12 +46,6 @@
 
 namespace grl {
 namespace {
-
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x4_t __attribute__((ext_vector_type(4)));
 
 constexpr int FG_R = 32;                  // destination rows per tile
 constexpr int FG_WAVES = 4;               // waves per workgroup
@@ -76,25 +71,6 @@ constexpr int FG_U = GRL_FG_U;            // neighbour rows in flight per wave
 constexpr int FG_CB = 8;                  // 32-column blocks of out (C <= 256, zero padded)
 constexpr int FG_FRAG = 64 * 8;           // bf16 per MFMA fragment (64 lanes x 8)
 
-// the x6 split, as linear.hip (same instructions, so the same bits)
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  f32x2_t p = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(p, bf16x2_t));
-}
-__device__ __forceinline__ float lo_f(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float hi_f(uint32_t u) { return __uint_as_float(u & 0xFFFF0000u); }
-
-__device__ __forceinline__ void split3(float4 v, uint2& p0, uint2& p1, uint2& p2) {
-  p0.x = pack_bf16(v.x, v.y);
-  p0.y = pack_bf16(v.z, v.w);
-  float4 r = make_float4(v.x - lo_f(p0.x), v.y - hi_f(p0.x), v.z - lo_f(p0.y), v.w - hi_f(p0.y));
-  p1.x = pack_bf16(r.x, r.y);
-  p1.y = pack_bf16(r.z, r.w);
-  r = make_float4(r.x - lo_f(p1.x), r.y - hi_f(p1.x), r.z - lo_f(p1.y), r.w - hi_f(p1.y));
-  p2.x = pack_bf16(r.x, r.y);
-  p2.y = pack_bf16(r.z, r.w);
-}
-
 __device__ __forceinline__ float4 zero4() { return make_float4(0.f, 0.f, 0.f, 0.f); }
 __device__ __forceinline__ void fma4(float4& acc, float w, const float4& x) {
   acc.x = __builtin_fmaf(w, x.x, acc.x);
@@ -106,8 +82,7 @@ __device__ __forceinline__ void fma4(float4& acc, float w, const float4& x) {
 // W [K][C] row-major -> three bf16 planes in MFMA B-fragment order:
 // Wf[ks][cb][q][lane][e] = plane q of W(k = 16 ks + 8 (lane >> 5) + e,
 // n = 32 cb + (lane & 31)) for cb < cbn (8: C <= 256, 16: C <= 512), zero for
-// n >= C.  Scalar split as
-// split_planes_kernel (linear.hip).
+// n >= C.
 // t_cin > 0 (the data-gradient form, grl_graphconv_bwd_data): W(k, n) is the
 // block-transposed forward weight, W(s t_cin + c, n) = Wfwd[s C + n][c] for
 // the forward's [(L+1) C][t_cin] h_weights (block s of the result = W_s^T).
@@ -122,15 +97,12 @@ __global__ void fused_w_planes_kernel(const float* __restrict__ W, int64_t K, in
     const int64_t k = ks * 16 + 8 * (lane >> 5) + e;
     const int n = cb * 32 + (lane & 31);
     const float v = n >= C ? 0.0f : (t_cin > 0 ? W[((k / t_cin) * C + n) * t_cin + k % t_cin] : W[k * C + n]);
-    const uint32_t h0 = pack_bf16(v, 0.0f) & 0xFFFFu;
-    const float r1 = v - lo_f(h0);
-    const uint32_t h1 = pack_bf16(r1, 0.0f) & 0xFFFFu;
-    const float r2 = r1 - lo_f(h1);
-    const uint32_t h2 = pack_bf16(r2, 0.0f) & 0xFFFFu;
+    uint16_t h0, h1, h2;
+    split1(v, h0, h1, h2);
     const int64_t o = (rest * 3) * FG_FRAG + lane * 8 + e;
-    Wf[o] = (uint16_t)h0;
-    Wf[o + FG_FRAG] = (uint16_t)h1;
-    Wf[o + 2 * FG_FRAG] = (uint16_t)h2;
+    Wf[o] = h0;
+    Wf[o + FG_FRAG] = h1;
+    Wf[o + 2 * FG_FRAG] = h2;
   }
 }
 
@@ -193,16 +165,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GRL_FG_WPE,
       const int ao = zoff(l32, 2 * ks + h);
 #pragma unroll
       for (int q = 0; q < 3; ++q) a[q] = *reinterpret_cast<const bf16x8_t*>(zs + q * FG_PLANE + ao);
-      // gemm_x6_kernel's product order: small terms first, the leading product last
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], bb[j][0], acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], bb[j][1], acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bb[j][2], acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], bb[j][0], acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bb[j][1], acc[j], 0, 0, 0);
-        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bb[j][0], acc[j], 0, 0, 0);
-      }
+      for (int j = 0; j < 2; ++j) x6_mfma(acc[j], a, bb[j]);
     };
 #if GRL_FG_BDEPTH == 2
     // ping-pong: the next step's W fragments are in flight during this step's MFMAs
@@ -802,17 +766,10 @@ __global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_kernel(
       for (int j = 0; j < WS_CB; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    // 12 MFMAs of row block i against both column blocks, gemm_x6_kernel's product order
+    // 12 MFMAs of row block i against both column blocks
     auto mma = [&](int i, const bf16x8_t (&b)[WS_CB][3], const bf16x8_t (&a)[3]) {
 #pragma unroll
-      for (int j = 0; j < WS_CB; ++j) {
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[j][0], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[j][1], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[j][2], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[j][0], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[j][1], acc[i][j], 0, 0, 0);
-        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[j][0], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < WS_CB; ++j) x6_mfma(acc[i][j], a, b[j]);
     };
     // this lane's 8 k (step ks) of row i*32 + l32 of a fp32 ring unit
     auto read_a = [&](const float* zs, int ks, int i, float4& v0, float4& v1) {

@@ -142,23 +142,44 @@ int device_cu_count();
 // Path options (grl_set_option / grl_get_option, include/grl.h): the test and
 // A/B hooks that select among kernel forms of one entry point.  Defaults are
 // the production choices; nothing in the library reads the environment.
+// One entry per option: X(enumerator, name, default, lo, hi).
+#define GRL_OPTIONS(X)                                                                    \
+  /* 1: split-bf16 (x6) GEMMs where sized for them; 0: fp32-MFMA kernels */               \
+  X(OPT_GEMM_X6, "gemm_x6", 1, 0, 1)                                                      \
+  /* 1: one-kernel GraphConv forward where eligible; 0: SpMM + GEMM */                    \
+  X(OPT_GRAPHCONV_FUSED, "graphconv_fused", 1, 0, 1)                                      \
+  /* 1: one-kernel GraphConv data gradient (read by the host layer) */                    \
+  X(OPT_GRAPHCONV_FUSED_BWD, "graphconv_fused_bwd", 1, 0, 1)                              \
+  /* 1: persistent warp-specialized one-kernel form; 0: phase-alternating */              \
+  X(OPT_FG_WS, "fg_ws", 1, 0, 1)                                                          \
+  /* -1: whole-row waves for tables > 12 GB; 1 / 0: always / never */                     \
+  X(OPT_SPMM_WIDE, "spmm_wide", -1, -1, 1)                                                \
+  /* SpMM workgroups per CU (24) */                                                       \
+  X(OPT_SPMM_BLOCKS_PER_CU, "spmm_blocks_per_cu", 24, 1, 64)                              \
+  /* 1: x6 attention kernels; 0: fp32-MFMA kernels */                                     \
+  X(OPT_ATTN_X6, "attn_x6", 1, 0, 1)                                                      \
+  /* 1: 8-wave pipelined forward; 0: 4-wave */                                            \
+  X(OPT_ATTN_FWD8, "attn_fwd8", 1, 0, 1)                                                  \
+  /* 1: 8-wave dH pass; 0: 4-wave */                                                      \
+  X(OPT_ATTN_DH8, "attn_dh8", 1, 0, 1)                                                    \
+  /* 1: dQ folded into the dK pass; 0: separate dQ kernel */                              \
+  X(OPT_ATTN_FUSED_DQ, "attn_fused_dq", 1, 0, 1)                                          \
+  /* 1: software-pipelined x6 forward; 0: unpipelined */                                  \
+  X(OPT_ATTN_PIPE, "attn_pipe", 1, 0, 1)                                                  \
+  /* 1: dH pass on 16x16x32 MFMAs (dk <= 16; default); 0: the 32x32x16 kernel */          \
+  X(OPT_ATTN_DH16, "attn_dh16", 1, 0, 1)                                                  \
+  /* 1: fused dK/dQ pass on 16x16x32 MFMAs (dk <= 16; default); 0: the 32x32x16 kernel */ \
+  X(OPT_ATTN_KQ16, "attn_kq16", 1, 0, 1)                                                  \
+  /* fused dK/dQ slab budget in bytes (0: 24 GiB) */                                      \
+  X(OPT_ATTN_QSLAB_MAX, "attn_qslab_max", 0, 0, INT64_MAX)                                \
+  /* persistent kernels' bounded-wait limit (0: 2^24 sleeps) */                           \
+  X(OPT_WS_SPIN, "ws_spin", 0, 0, (int64_t)1 << 30)                                       \
+  /* 1: an eager one-kernel call checks its own status (debug) */                         \
+  X(OPT_WS_STATUS_SYNC, "ws_status_sync", 0, 0, 1)
 enum GrlOpt {
-  OPT_GEMM_X6,              // 1: split-bf16 (x6) GEMMs where sized for them; 0: fp32-MFMA kernels
-  OPT_GRAPHCONV_FUSED,      // 1: one-kernel GraphConv forward where eligible; 0: SpMM + GEMM
-  OPT_GRAPHCONV_FUSED_BWD,  // 1: one-kernel GraphConv data gradient (read by the host layer)
-  OPT_FG_WS,                // 1: persistent warp-specialized one-kernel form; 0: phase-alternating
-  OPT_SPMM_WIDE,            // -1: whole-row waves for tables > 12 GB; 1 / 0: always / never
-  OPT_SPMM_BLOCKS_PER_CU,   // SpMM workgroups per CU (24)
-  OPT_ATTN_X6,              // 1: x6 attention kernels; 0: fp32-MFMA kernels
-  OPT_ATTN_FWD8,            // 1: 8-wave pipelined forward; 0: 4-wave
-  OPT_ATTN_DH8,             // 1: 8-wave dH pass; 0: 4-wave
-  OPT_ATTN_FUSED_DQ,        // 1: dQ folded into the dK pass; 0: separate dQ kernel
-  OPT_ATTN_PIPE,            // 1: software-pipelined x6 forward; 0: unpipelined
-  OPT_ATTN_DH16,            // 1: dH pass on 16x16x32 MFMAs (dk <= 16; default); 0: the 32x32x16 kernel
-  OPT_ATTN_KQ16,            // 1: fused dK/dQ pass on 16x16x32 MFMAs (dk <= 16; default); 0: the 32x32x16 kernel
-  OPT_ATTN_QSLAB_MAX,       // fused dK/dQ slab budget in bytes (0: 24 GiB)
-  OPT_WS_SPIN,              // persistent kernels' bounded-wait limit (0: 2^24 sleeps)
-  OPT_WS_STATUS_SYNC,       // 1: an eager one-kernel call checks its own status (debug)
+#define GRL_OPT_ENUM(id, name, def, lo, hi) id,
+  GRL_OPTIONS(GRL_OPT_ENUM)
+#undef GRL_OPT_ENUM
   OPT_COUNT
 };
 int64_t opt(GrlOpt o);

@@ -18,6 +18,7 @@
 // (dW sums over all N nodes) split K over blockIdx.z into fp32 slabs that a
 // second pass adds in split order: deterministic, no atomics.
 #include "grl_internal.h"
+#include "x6.h"
 
 
 #include <cstdlib>
@@ -41,7 +42,6 @@
 namespace grl {
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
 
 constexpr int BM = 128, BN = 128;
 
@@ -460,22 +460,8 @@ struct PipeOperand {
         col = col + 3 < rows_total ? col : rows_total - 4;
         src = base + (k0 + inst) * ld + col;
       }
-      // Issued from asm so that the compiler's waitcnt pass does not see an
-      // LDS write in flight and wait vmcnt(0) before every ds_read (which
-      // would serialize the pipeline); ordering is the counted vmcnt +
-      // s_barrier in the kernel.  M0 = the wave-uniform LDS byte address.
-      const uint32_t dst = __builtin_amdgcn_readfirstlane(
-          (uint32_t)reinterpret_cast<uintptr_t>(lds + inst * 256));
-      uint32_t keep;
-      asm volatile(
-          "s_mov_b32 %0, m0\n\t"
-          "s_mov_b32 m0, %2\n\t"
-          "s_nop 0\n\t"
-          "global_load_lds_dwordx4 %1, off\n\t"
-          "s_mov_b32 m0, %0"
-          : "=&s"(keep)
-          : "v"(src), "s"(dst)
-          : "memory");
+      // ordering is the counted vmcnt + s_barrier in the kernel
+      dma16(src, lds + inst * 256);
     }
   }
   __device__ __forceinline__ static float4 frag(const float* lds, int row, int kk, int h) {
@@ -605,32 +591,9 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmArgs p) {
 // B arrive by LDS-DMA (layout and pipeline at gemm_x6_kernel below).
 // Preconditions (x6_shape_ok + aligned): K % 16 == 0, 16-B aligned A,
 // lda % 4 == 0, no operand masks.
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-
 constexpr int X6_K = 16;
 constexpr int X6_PLANE = 256 * X6_K;  // bf16 elements per plane per operand stage
 constexpr int X6_STAGE = 6 * X6_PLANE;  // A planes then B planes
-
-__device__ __forceinline__ uint32_t pack_bf16(float a, float b) {
-  f32x2_t p = {a, b};
-  return __builtin_bit_cast(uint32_t, __builtin_convertvector(p, bf16x2_t));
-}
-__device__ __forceinline__ float lo_f(uint32_t u) { return __uint_as_float(u << 16); }
-__device__ __forceinline__ float hi_f(uint32_t u) { return __uint_as_float(u & 0xFFFF0000u); }
-
-// v -> three planes of 4 bf16 (v == p0 + p1 + p2 exactly)
-__device__ __forceinline__ void split3(float4 v, uint2& p0, uint2& p1, uint2& p2) {
-  p0.x = pack_bf16(v.x, v.y);
-  p0.y = pack_bf16(v.z, v.w);
-  float4 r = make_float4(v.x - lo_f(p0.x), v.y - hi_f(p0.x), v.z - lo_f(p0.y), v.w - hi_f(p0.y));
-  p1.x = pack_bf16(r.x, r.y);
-  p1.y = pack_bf16(r.z, r.w);
-  r = make_float4(r.x - lo_f(p1.x), r.y - hi_f(p1.x), r.z - lo_f(p1.y), r.w - hi_f(p1.y));
-  p2.x = pack_bf16(r.x, r.y);
-  p2.y = pack_bf16(r.z, r.w);
-}
 
 // planes[p][n][k] (n < Np, k < K; zero for n >= N) of B(k, n) = B_KC ? B[n*ldb + k] : B[k*ldb + n]
 __global__ void split_planes_kernel(const float* __restrict__ B, int64_t ldb, int b_kc, int64_t N, int64_t K,
@@ -639,32 +602,12 @@ __global__ void split_planes_kernel(const float* __restrict__ B, int64_t ldb, in
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t n = i / K, k = i - n * K;
     const float v = n < N ? (b_kc ? B[n * ldb + k] : B[k * ldb + n]) : 0.0f;
-    const uint32_t h0 = pack_bf16(v, 0.0f) & 0xFFFFu;
-    const float r1 = v - lo_f(h0);
-    const uint32_t h1 = pack_bf16(r1, 0.0f) & 0xFFFFu;
-    const float r2 = r1 - lo_f(h1);
-    const uint32_t h2 = pack_bf16(r2, 0.0f) & 0xFFFFu;
-    planes[i] = (uint16_t)h0;
-    planes[total + i] = (uint16_t)h1;
-    planes[2 * total + i] = (uint16_t)h2;
+    uint16_t h0, h1, h2;
+    split1(v, h0, h1, h2);
+    planes[i] = h0;
+    planes[total + i] = h1;
+    planes[2 * total + i] = h2;
   }
-}
-
-// global -> LDS DMA of one 16 B chunk per lane (lane l lands at lds_base + 16 l).
-// Issued from asm so that hipcc's waitcnt pass neither sees nor waits on it;
-// completion is ordered by the kernel's counted `s_waitcnt vmcnt`.
-__device__ __forceinline__ void dma16(const void* src, const void* lds_base) {
-  const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)reinterpret_cast<uintptr_t>(lds_base));
-  uint32_t keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(src), "s"(dst)
-      : "memory");
 }
 
 // LDS: two plane stages (48 KB each: A planes 0-2, B planes 3-5, 256 rows x
@@ -775,18 +718,10 @@ __global__ __launch_bounds__(512) void gemm_x6_kernel(GemmArgs p, const uint16_t
 #pragma unroll
         for (int q = 0; q < 3; ++q)
           b_[j][q] = *reinterpret_cast<const bf16x8_t*>(cur + (3 + q) * X6_PLANE + sw(wn * 64 + j * 32 + l32, h * 8));
-      // small terms first (i + j = 2, then 1, then the leading product)
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][2], b_[j][0], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][1], b_[j][1], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][0], b_[j][2], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][1], b_[j][0], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][0], b_[j][1], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][0], b_[j][0], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < 2; ++j) x6_mfma(acc[i][j], a_[i], b_[j]);
     }
     if (t + 1 < nk) {
       if (t + 2 < nk)
@@ -846,22 +781,6 @@ __global__ __launch_bounds__(512) void gemm_x6_kernel(GemmArgs p, const uint16_t
 // split order afterwards (deterministic).  Register-staged: the next step's
 // loads are in flight during the MFMAs.  Preconditions (x6t_ok): 16-B
 // aligned operands, lda, ldb, M, N multiples of 4.
-typedef short i16x4_t __attribute__((ext_vector_type(4)));
-
-typedef __attribute__((address_space(3))) uint16_t lds_u16;
-
-// tr_pair on an LDS-space pointer (p0 = plane + k * 256 + swizzled column):
-// the second block row is a constant 2 KB further, so with the stage and the
-// plane also constants both reads fold into one base VGPR + ds offsets
-__device__ __forceinline__ bf16x8_t tr_pair3(const lds_u16* p0) {
-  typedef __attribute__((address_space(3))) i16x4_t lds_v4;
-  const i16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)p0);
-  const i16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(p0 + 4 * 256));
-  typedef short i16x8_t __attribute__((ext_vector_type(8)));
-  const i16x8_t v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-  return __builtin_bit_cast(bf16x8_t, v);
-}
-
 // The K16 loop is unrolled over the two stages, fragment reads from per-lane
 // LDS offsets fixed for the kernel (the stage and plane as immediates): the
 // rolled loop recomputed ~40 address adds per step (round 4,
@@ -974,26 +893,22 @@ __global__ __launch_bounds__(512) void gemm_x6t_kernel(GemmArgs p) {
       constexpr int S = decltype(stage)::value;
       constexpr int J = decltype(rset)::value;  // (t + 1) % NR
       const lds_u16* cur = s3 + S * X6_STAGE;
+      // a fragment's two transposed reads: the second block row is a constant 2 KB (4 k rows) further, so
+      // with the stage and the plane also constants both reads fold into one base VGPR + ds offsets
+      auto frag = [](const lds_u16* p0) { return tr8s(p0, p0 + 4 * 256); };
       bf16x8_t a_[4][3], b_[2][3];
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int q = 0; q < 3; ++q) a_[i][q] = tr_pair3(cur + q * X6_PLANE + oa[i]);
+        for (int q = 0; q < 3; ++q) a_[i][q] = frag(cur + q * X6_PLANE + oa[i]);
 #pragma unroll
       for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int q = 0; q < 3; ++q) b_[j][q] = tr_pair3(cur + (3 + q) * X6_PLANE + ob[j]);
+        for (int q = 0; q < 3; ++q) b_[j][q] = frag(cur + (3 + q) * X6_PLANE + ob[j]);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][2], b_[j][0], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][1], b_[j][1], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][0], b_[j][2], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][1], b_[j][0], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][0], b_[j][1], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a_[i][0], b_[j][0], acc[i][j], 0, 0, 0);
-        }
+        for (int j = 0; j < 2; ++j) x6_mfma(acc[i][j], a_[i], b_[j]);
       if (t + 1 < nk) {
         X6T_STASH(smem + (S ^ 1) * X6_STAGE, J);  // the other stage: last read in step t-1
 #if GRL_X6T_WHATIF & 2

@@ -8,6 +8,12 @@ the pinned kernels' instruction streams (comments, directives and label
 names normalised away) and hashes them.  tests/test_codegen_pin.py compares
 the hashes with tests/golden/codegen_pins.json: a mismatch means "re-measure
 the kernel on the GPU and re-pin" (python tools/pin_codegen.py --write).
+
+--all [--root TREE] hashes every kernel of every source in the Makefile's SRCS
+instead, each file with its own flags (the per-object HIPFLAGS additions
+included), and prints {source: {kernel symbol: {instructions, sha256}}}: two
+trees whose outputs are equal build the same machine code.  It reads and
+writes no pin.
 """
 import hashlib
 import json
@@ -16,6 +22,7 @@ import re
 import subprocess
 import sys
 import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 CSRC = os.path.join(ROOT, "graph-representation-learning_amd", "csrc")
@@ -74,7 +81,47 @@ def compute():
     return res
 
 
+def makefile_flags(csrc):
+    """SRCS and each source's HIPFLAGS as csrc/Makefile gives them to the object rule."""
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    root = os.path.abspath(os.path.join(csrc, "..", ".."))
+    var = {"ARCH": "gfx950", "ROOT": root}
+    sub = lambda v: re.sub(r"\$\((\w+)\)", lambda m: var[m.group(1)], v)
+    srcs = re.search(r"^SRCS\s*:=\s*(.*)$", mk, re.M).group(1).split()
+    base = sub(re.search(r"^HIPFLAGS\s*:=\s*(.*)$", mk, re.M).group(1)).split()
+    flags = {}
+    for src in srcs:
+        stem = src[:-len(".hip")]
+        extra = re.findall(r"^\$\(OBJDIR\)/" + re.escape(stem) + r"\.o:\s*HIPFLAGS\s*\+=\s*(.*)$", mk, re.M)
+        flags[src] = base + [f for e in extra for f in sub(e).split()] + ["-cuid=grl_" + stem]
+    return srcs, flags
+
+
+def compute_all(root):
+    csrc = os.path.join(root, "graph-representation-learning_amd", "csrc")
+    srcs, flags = makefile_flags(csrc)
+
+    def one(src):
+        with tempfile.TemporaryDirectory() as tmp:
+            out = os.path.join(tmp, src + ".s")
+            subprocess.run([HIPCC] + flags[src] + ["--cuda-device-only", "-S", src, "-o", out], cwd=csrc, check=True,
+                           capture_output=True)
+            asm = open(out).read()
+        res = {}
+        for sym in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)", asm, re.M):
+            text, n = kernel_stream(asm, sym)
+            res[sym] = {"instructions": n, "sha256": hashlib.sha256(text.encode()).hexdigest()}
+        return src, res
+
+    with ThreadPoolExecutor(max_workers=min(8, len(srcs))) as ex:
+        return dict(ex.map(one, srcs))
+
+
 if __name__ == "__main__":
+    if "--all" in sys.argv:
+        root = sys.argv[sys.argv.index("--root") + 1] if "--root" in sys.argv else ROOT
+        print(json.dumps(compute_all(os.path.abspath(root)), indent=1, sort_keys=True))
+        sys.exit(0)
     pins = compute()
     if "--write" in sys.argv:
         with open(PINS, "w") as f:
