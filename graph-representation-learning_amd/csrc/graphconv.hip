@@ -23,6 +23,10 @@
 // order, the same DropEdge weights), split and multiplied in the same K16
 // order and product order as gemm_x6_kernel, so the result is bitwise that
 // of the two-kernel path (tests/test_gpu_graphconv.py).
+//
+// The grl_graphconv_* entry points and the rules that choose between these
+// kernels and the SpMM + GEMM chain are at the end of this file; from
+// spmm.hip and linear.hip they take what grl_internal.h declares.
 #include <cstring>
 
 #include "grl_internal.h"
@@ -354,7 +358,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(GRL_FG_WPE,
     }
   }
 }
-
 
 // ---------------------------------------------------------------------------
 // Warp-specialized persistent form (the default).  One workgroup per CU, 12
@@ -907,14 +910,14 @@ extern "C" int grl_debug_ws_stats(unsigned long long* host, int64_t n) {
 
 // The graphconv_fused path option 0 keeps grl_graphconv_fwd on the
 // two-kernel path (A/B aid and tests).
-bool graphconv_fused_enabled() { return opt(OPT_GRAPHCONV_FUSED) != 0; }
+static bool graphconv_fused_enabled() { return opt(OPT_GRAPHCONV_FUSED) != 0; }
 
 // The gathered width F: one virtual segment (64, 128, 256) or 2 / 4 of 256
 // columns; the output width C <= 512 (C > 256: 4 gather + 8 MFMA waves); L
 // <= 7 (a gather wave's rowptr window holds RW L + 1 entries in 1 or 2
 // registers).  The phase-alternating kernel (fg_ws = 0) takes F <= 256, C
 // <= 256 only; other shapes always run the persistent one.
-bool graphconv_fused_shape_ok(int F, int C, int L) {
+static bool graphconv_fused_shape_ok(int F, int C, int L) {
   return (F == 64 || F == 128 || F == 256 || F == 512 || F == 1024) && C >= 1 && C <= 512 && L >= 1 && L <= 7;
 }
 
@@ -922,7 +925,7 @@ bool graphconv_fused_shape_ok(int F, int C, int L) {
 static int planes_cb(int C) { return C <= 256 ? FG_CB : 2 * FG_CB; }
 
 // W's planes, then 256 B whose first word is the call's status
-size_t graphconv_fused_ws_bytes(int64_t K, int C) { return (size_t)K * planes_cb(C) * 32 * 3 * 2 + 256; }
+static size_t graphconv_fused_ws_bytes(int64_t K, int C) { return (size_t)K * planes_cb(C) * 32 * 3 * 2 + 256; }
 
 static int* ws_status(void* ws, int64_t K, int C) {
   return reinterpret_cast<int*>(static_cast<char*>(ws) + (size_t)K * planes_cb(C) * 32 * 3 * 2);
@@ -1018,10 +1021,11 @@ static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M
 #undef GRL_WS_ARGS
 }
 
-int graphconv_fused_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int F, const float* W, const float* bias,
-                        int C, int relu, float* out, const GrlDropEdge* de, void* ws, hipStream_t st, float* Z) {
+static int graphconv_fused_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int F, const float* W,
+                               const float* bias, int C, int relu, float* out, const GrlDropEdge* de, void* ws,
+                               hipStream_t st, float* Z = nullptr) {
   const int hs = g->has_self ? 1 : 0;
-  const int64_t K = (int64_t)(g->num_types + hs) * F;
+  const int64_t K = (int64_t)segments(g) * F;
   uint16_t* Wf = static_cast<uint16_t*>(ws);
   const int cbn = planes_cb(C);
   const int64_t n_el = K * cbn * 32;
@@ -1072,11 +1076,11 @@ int graphconv_fused_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int F
 // graphconv_ws_kernel with the rows' CSC segments, DropEdge ids through eid,
 // and W's planes taken block-transposed.  Cin = G's width (the forward's C),
 // Cout = dX's width (the forward's F).
-int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const float* G, int64_t ldg, int64_t self_rows,
-                             int Cin, const float* W, int Cout, float* dX, float* Gagg, const GrlDropEdge* de, void* ws,
-                             hipStream_t st) {
+static int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const float* G, int64_t ldg,
+                                    int64_t self_rows, int Cin, const float* W, int Cout, float* dX, float* Gagg,
+                                    const GrlDropEdge* de, void* ws, hipStream_t st) {
   const int hs = gt->has_self ? 1 : 0;
-  const int64_t K = (int64_t)(gt->num_types + hs) * Cin;
+  const int64_t K = (int64_t)segments(gt) * Cin;
   uint16_t* Wf = static_cast<uint16_t*>(ws);
   const int cbn = planes_cb(Cout);
   const int64_t n_el = K * cbn * 32;
@@ -1098,7 +1102,171 @@ int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const fl
   return graphconv_status(status, dX, M * Cout, Gagg, M * K, st, WS_WHO_BWD_DATA);
 }
 
+// ---- the layer's dispatch: which kernels a grl_graphconv_* call runs -------
+static size_t ws_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// the two-kernel form's workspace for a graph whose GEMM path is chosen for path_rows rows
+static size_t graphconv_two_kernel_ws(const GrlTypedCsr* g, int F, int C) {
+  const int64_t K = (int64_t)segments(g) * F;
+  return ws_align((size_t)g->num_rows * (size_t)K * 4) +
+         grl_linear_fwd_ex_workspace_size(g->num_rows, (int32_t)K, C, g->path_rows);
+}
+
+// grl_graphconv_fwd takes the fused kernel when its arithmetic equals the
+// two-kernel path's (the linear on the x6 GEMM: large graphs, 16-B aligned W,
+// C % 4 == 0), the shapes fit it (graphconv_fused_shape_ok), X rows are
+// float4-aligned and no heavy row is split (the split path sums chunk
+// partials, a different order).
+static bool fused_path(const GrlTypedCsr* g, const float* X, int64_t ldx, int F, const float* W, int C) {
+  return graphconv_fused_enabled() && graphconv_fused_shape_ok(F, C, g->num_types) &&
+         x6_path_ok(g->num_rows, g->path_rows, C, (int64_t)segments(g) * F) &&
+         al16(W) && C % 4 == 0 && al16(X) && ldx % 4 == 0 && ldx < (1LL << 30) &&  // gather: 32-bit row bytes
+         (!g->split || g->split->num_heavy == 0);
+}
+
+// The data gradient of one GraphConv layer by reassociation (see grl.h):
+// dX = sum_s (A_drop,s^T G) W_s^T on the one-kernel GraphConv over the typed
+// transpose.  Eligible when the shape is (grl_graphconv_bwd_data_shape_ok) and
+// the call's pointers and plan are: a whole-range transpose, W and G rows
+// float4-aligned, no heavy-row split plan, int32 entries.
+static bool bwd_data_path(const GrlTypedCsr* gt, const float* G, int64_t ldg, int C, const float* W, int F) {
+  return grl_graphconv_bwd_data_shape_ok(gt->num_rows, gt->num_types, gt->has_self, C, F) && gt->self_row0 == 0 &&
+         al16(W) && al16(G) && ldg % 4 == 0 && ldg < (1LL << 30) && (!gt->split || gt->split->num_heavy == 0) &&
+         gt->nnz < 2147483647LL;
+}
+
+// What grl_graphconv_fwd and _fwd_train check alike (`outs`: their outputs are
+// non-NULL); *K = the linear's depth, set for a graph with rows.
+static int graphconv_fwd_check(const char* who, const GrlTypedCsr* g, const float* X, int64_t ldx, int F,
+                               const float* W, int C, bool outs, const void* ws, int32_t* K) {
+  const int rc = csr_fwd_check(who, g, F, ldx, X && W && outs);
+  if (rc) return rc;
+  GRL_CHECK_ARG(C > 0, "%s: need C > 0 (got %d)", who, C);
+  if (g->num_rows == 0) return GRL_OK;
+  const int64_t K64 = (int64_t)segments(g) * F;
+  GRL_CHECK_ARG(K64 <= 2147483647LL, "%s: (has_self + num_types) * F exceeds int32", who);
+  GRL_CHECK_ARG(ws == nullptr || al16(ws), "%s: workspace must be 16-B aligned", who);
+  *K = (int32_t)K64;
+  return GRL_OK;
+}
+
 }  // namespace grl
+
+using namespace grl;
+
+extern "C" size_t grl_graphconv_fwd_workspace_query(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F,
+                                                   const float* W, int32_t C) {
+  if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0) return 0;
+  const int64_t K = (int64_t)segments(g) * F;
+  if (K > 2147483647LL) return 0;
+  if (fused_path(g, X, ldx, F, W, C)) return graphconv_fused_ws_bytes(K, C);
+  return graphconv_two_kernel_ws(g, F, C);
+}
+
+extern "C" size_t grl_graphconv_fwd_workspace_size(int64_t num_rows, int32_t num_types, int32_t has_self, int32_t F,
+                                                   int32_t C) {
+  if (num_rows <= 0 || num_types < 1 || F <= 0 || C <= 0) return 0;
+  const int64_t K = (int64_t)segments(num_types, has_self) * F;
+  if (K > 2147483647LL) return 0;
+  return ws_align((size_t)num_rows * (size_t)K * 4) + grl_linear_fwd_workspace_size(num_rows, (int32_t)K, C);
+}
+
+extern "C" int grl_graphconv_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
+                                 const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
+                                 void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  TraceRange trace_("grl_graphconv_fwd");
+  int32_t K = 0;
+  int rc = graphconv_fwd_check("grl_graphconv_fwd", g, X, ldx, F, W, C, out != nullptr, workspace, &K);
+  if (rc || g->num_rows == 0) return rc;
+  const int64_t M = g->num_rows;
+  hipStream_t st = as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  const size_t zfull = ws_align((size_t)M * (size_t)K * 4);
+  if (fused_path(g, X, ldx, F, W, C) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, ws, st);  // one kernel: Z never leaves the CU
+  if (ws && workspace_bytes >= graphconv_two_kernel_ws(g, F, C)) {
+    // whole graph: Z in the workspace, then the linear (its workspace behind Z)
+    float* Z = reinterpret_cast<float*>(ws);
+    rc = grl_typed_spmm_fwd(g, X, ldx, F, Z, de, stream);
+    if (rc) return rc;
+    return grl_linear_fwd_ex(Z, K, W, 0, bias, out, M, K, C, relu, g->path_rows, ws + zfull, workspace_bytes - zfull,
+                             stream);
+  }
+  // Row chunks: Z for R rows at a time (bounded memory), on the x6 GEMM only,
+  // whose per-element arithmetic does not depend on M -- so the result is
+  // bitwise that of the whole-graph call.
+  const bool x6 = x6_path_ok(M, g->path_rows, C, K) && al16(W) && C % 4 == 0;
+  if (!x6 || (g->split && g->split->num_heavy > 0) || !ws)
+    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_fwd: workspace %zu < %zu (row chunking needs the x6 GEMM shape and no "
+             "heavy-row split plan)", workspace_bytes,
+             grl_graphconv_fwd_workspace_size(M, g->num_types, g->has_self, F, C));
+  const size_t planes_bytes = ws_align(x6_ws_bytes_p(M, g->path_rows, C, K));
+  const int64_t per_row = (int64_t)K * 4;
+  int64_t R = workspace_bytes > planes_bytes ? (int64_t)((workspace_bytes - planes_bytes) / per_row) : 0;
+  R = R / LB_M * LB_M;
+  if (R < LB_M)
+    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_fwd: workspace %zu holds fewer than %d rows of Z", workspace_bytes, LB_M);
+  uint16_t* planes = reinterpret_cast<uint16_t*>(ws);
+  float* Z = reinterpret_cast<float*>(ws + planes_bytes);
+  rc = x6_split_w(W, K, C, planes, st);
+  for (int64_t r0 = 0; r0 < M && !rc; r0 += R) {
+    const int64_t rows = std::min<int64_t>(R, M - r0);
+    rc = spmm_fwd_rows(g, r0, rows, X, ldx, F, Z, de, st);
+    if (!rc) rc = x6_gemm_rows(Z, rows, K, planes, C, bias, relu, out + r0 * C, st);
+  }
+  return rc;
+}
+
+extern "C" int grl_graphconv_fwd_train(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
+                                       const float* bias, int32_t C, int32_t relu, float* out, float* Z,
+                                       const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
+                                       grl_stream_t stream) {
+  TraceRange trace_("grl_graphconv_fwd_train");
+  int32_t K = 0;
+  int rc = graphconv_fwd_check("grl_graphconv_fwd_train", g, X, ldx, F, W, C, out && Z, workspace, &K);
+  if (rc || g->num_rows == 0) return rc;
+  if (fused_path(g, X, ldx, F, W, C) && al16(Z) && workspace && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, workspace, as_stream(stream), Z);
+  rc = grl_typed_spmm_fwd(g, X, ldx, F, Z, de, stream);
+  return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, g->num_rows, K, C, relu, g->path_rows, workspace,
+                                     workspace_bytes, stream);
+}
+
+extern "C" int32_t grl_graphconv_bwd_data_shape_ok(int64_t rows, int32_t num_types, int32_t has_self, int32_t C,
+                                                   int32_t F) {
+  const int64_t K = (int64_t)segments(num_types, has_self) * C;
+  return graphconv_fused_enabled() && graphconv_fused_shape_ok(C, F, num_types) && x6_path_ok(rows, 0, F, K) &&
+         F % 4 == 0 && K <= 2147483647LL;
+}
+
+extern "C" size_t grl_graphconv_bwd_data_workspace_query(const GrlTypedCsr* gt, const float* G, int64_t ldg, int32_t C,
+                                                        const float* W, int32_t F) {
+  if (!gt || gt->num_rows <= 0 || gt->num_types < 1 || C <= 0 || F <= 0) return 0;
+  return bwd_data_path(gt, G, ldg, C, W, F) ? graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F) : 0;
+}
+
+extern "C" int grl_graphconv_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const float* G, int64_t ldg,
+                                      int64_t g_rows, int32_t C, const float* W, int32_t F, float* dX, float* G_agg,
+                                      const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
+                                      grl_stream_t stream) {
+  TraceRange trace_("grl_graphconv_bwd_data");
+  GRL_CHECK_ARG(gt != nullptr, "grl_graphconv_bwd_data: graph is NULL");
+  GRL_CHECK_ARG(gt->num_rows >= 0 && gt->num_types >= 1 && gt->num_types <= 63,
+                "grl_graphconv_bwd_data: num_types must be in [1, 63] (got %d)", gt->num_types);
+  GRL_CHECK_ARG(C > 0 && ldg >= C && F > 0 && g_rows >= 0 && g_rows <= gt->num_rows,
+                "grl_graphconv_bwd_data: need C > 0, ldg >= C, F > 0, 0 <= g_rows <= num_rows");
+  if (gt->num_rows == 0) return GRL_OK;
+  // (an empty node-range shard: no G rows and no entries, so its empty G is never read)
+  GRL_CHECK_ARG((G || (g_rows == 0 && gt->nnz == 0)) && W && dX && gt->rowptr && (gt->nnz == 0 || (gt->colidx && eid)),
+                "grl_graphconv_bwd_data: NULL pointer");
+  if (!bwd_data_path(gt, G, ldg, C, W, F))
+    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_graphconv_bwd_data: shape outside the one-kernel path (C %d, F %d, L %d, rows "
+             "%lld; see grl_graphconv_bwd_data_workspace_query)", C, F, gt->num_types, (long long)gt->num_rows);
+  const size_t need = graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F);
+  if (!workspace || !al16(workspace) || workspace_bytes < need)
+    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_bwd_data: workspace %zu < %zu (16-B aligned)", workspace_bytes, need);
+  return graphconv_fused_bwd_data(gt, eid, G, ldg, g_rows, C, W, F, dX, G_agg, de, workspace, as_stream(stream));
+}
 
 namespace grl {
 namespace {

@@ -65,20 +65,34 @@ __host__ __device__ __forceinline__ uint64_t synth_bits(uint64_t seed, uint64_t 
   return mix64(mix64(seed + 0x243F6A8885A308D3ull * (uint64_t)(lane + 1)) ^ (k * 0x9E3779B97F4A7C15ull));
 }
 
-// Row-range typed-SpMM forward (spmm.hip) used by grl_graphconv_fwd.
+// Segments of a Z row: the identity block (has_self) and one per edge type.
+inline int segments(int num_types, int has_self) { return num_types + (has_self ? 1 : 0); }
+inline int segments(const GrlTypedCsr* g) { return segments(g->num_types, g->has_self); }
+
+inline bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
+
+// ---- what the GraphConv layer (graphconv.hip: the grl_graphconv_* entry
+// points and their dispatch) takes from the primitives ----------------------
+// spmm.hip.  The argument check the forward entry points over a typed CSR
+// share (grl_typed_spmm_fwd, _fwd_slice, grl_graphconv_fwd, _fwd_train): the
+// graph, its type count, F and ldx, and -- for a graph with rows -- the
+// pointers (`ptrs`: the entry point's own are non-NULL), nnz and self_row0.
+int csr_fwd_check(const char* who, const GrlTypedCsr* g, int F, int64_t ldx, bool ptrs);
+// Row-range typed-SpMM forward: grl_graphconv_fwd's row chunks.
 int spmm_fwd_rows(const GrlTypedCsr* g, int64_t r0, int64_t rows, const float* X, int64_t ldx, int F, float* Z,
                   const GrlDropEdge* de, hipStream_t st);
 
-// Fused one-kernel GraphConv forward (graphconv.hip), used by grl_graphconv_fwd.
-bool graphconv_fused_enabled();
-bool graphconv_fused_shape_ok(int F, int C, int L);
-size_t graphconv_fused_ws_bytes(int64_t K, int C);
-int graphconv_fused_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int F, const float* W, const float* bias,
-                        int C, int relu, float* out, const GrlDropEdge* de, void* ws, hipStream_t st,
-                        float* Z = nullptr);
-int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const float* G, int64_t ldg, int64_t self_rows,
-                             int Cin, const float* W, int Cout, float* dX, float* Gagg, const GrlDropEdge* de, void* ws,
-                             hipStream_t st);
+// linear.hip.  Whether an [M, K] x [K, N] product chosen for max(M,
+// path_rows) rows takes the x6 GEMM, and the bytes of W's planes if so (else
+// 0); W [K, N] row-major split into those planes; the x6 GEMM of `rows` rows
+// of A [rows, K] on planes already split (out [rows, N] contiguous), whose
+// bits do not depend on `rows`; LB_M, its row tile.
+constexpr int LB_M = 256;
+bool x6_path_ok(int64_t M, int64_t path_rows, int64_t N, int64_t K);
+size_t x6_ws_bytes_p(int64_t M, int64_t path_rows, int64_t N, int64_t K);
+int x6_split_w(const float* W, int64_t K, int64_t N, uint16_t* planes, hipStream_t st);
+int x6_gemm_rows(const float* A, int64_t rows, int64_t K, const uint16_t* planes, int64_t N, const float* bias,
+                 int relu, float* out, hipStream_t st);
 
 // Plain-data copy of GrlDropEdge passed by value to kernels.
 struct DropDev {

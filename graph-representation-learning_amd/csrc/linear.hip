@@ -20,7 +20,6 @@
 #include "grl_internal.h"
 #include "x6.h"
 
-
 #include <cstdlib>
 
 // GRL_X6T_WHATIF (diagnostic builds with -DGRL_DIAG only; timing, wrong
@@ -42,10 +41,7 @@
 namespace grl {
 namespace {
 
-
 constexpr int BM = 128, BN = 128;
-
-
 
 enum Epilogue { EPI_STORE = 0, EPI_BIAS = 1, EPI_SLAB = 2 };
 
@@ -71,6 +67,11 @@ struct GemmArgs {
   int64_t path_rows;
 };
 
+// C (M x N, ldc) = A (M x K, lda) B (K x N, ldb); everything else unset
+GemmArgs gemm_args(const float* A, int64_t lda, const float* B, int64_t ldb, float* C, int64_t ldc, int64_t M,
+                   int64_t N, int64_t K) {
+  return GemmArgs{A, lda, nullptr, B, ldb, nullptr, C, ldc, nullptr, M, N, K};
+}
 
 // XCD-aware tile order.  Workgroups are dealt to the 8 XCDs round-robin
 // (blockIdx % 8; speed only, never relied on for correctness), and each XCD
@@ -435,7 +436,7 @@ __global__ __launch_bounds__(256) void relu_grad_colsum_kernel(const float* g, c
 // contiguous) stays on the 128^2 kernel (7.8 ms vs 10.6 here).
 // Preconditions (big_ok): 16-B aligned operands and leading dimensions,
 // K % 16 == 0, M, N >= 4, no operand masks.
-constexpr int LB_M = 256, LB_N = 256;
+constexpr int LB_N = 256;  // (LB_M, the row tile: grl_internal.h)
 constexpr int LP_K = 16, LP_STAGE = LB_M * LP_K;  // floats per operand stage
 
 template <bool KC>
@@ -565,7 +566,6 @@ __global__ __launch_bounds__(512) void gemm256p_kernel(GemmArgs p) {
       }
   }
 }
-
 
 // ---------------------------------------------------------------------------
 // fp32 GEMM on the bf16 matrix cores by exact three-way splitting ("x6").
@@ -958,8 +958,6 @@ __global__ __launch_bounds__(512) void gemm_x6t_kernel(GemmArgs p) {
   }
 }
 
-bool al16(const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; }
-
 constexpr int GEMM_BK = 32;
 
 template <bool A_KC, bool B_KC, int EPI, int TBN = BN>
@@ -1058,10 +1056,15 @@ size_t small_ws_bytes(int64_t M, int64_t path_rows, int64_t N, int64_t K) {
   return s > 1 ? (size_t)s * (size_t)fp32_block_rows(M, N, s) * (size_t)N * 4 + 256 : 0;
 }
 
+// The size floor of the 256 x 256 tile kernels (x6, x6t and the pipelined
+// fp32 tile), in flops 2 M N K of the whole product: smaller products run on
+// the 128 x 128 kernel.  The one place the floor is written (grl.h quotes it).
+constexpr double kBigGemmFlops = 1.6e10;
+bool big_flops(int64_t M, int64_t N, int64_t K) { return 2.0 * (double)M * (double)N * (double)K >= kBigGemmFlops; }
+
 // Large-tile path selection (the fp32 fallback when the x6 path is off).
 bool big_ok(const GemmArgs& a, bool aligned) {
-  return aligned && !a.Amask && !a.Bmask && a.K % LP_K == 0 && a.M >= 4 && a.N >= 4 &&
-         2.0 * (double)a.M * (double)a.N * (double)a.K >= 1.6e10;
+  return aligned && !a.Amask && !a.Bmask && a.K % LP_K == 0 && a.M >= 4 && a.N >= 4 && big_flops(a.M, a.N, a.K);
 }
 
 template <bool A_KC, bool B_KC, int EPI>
@@ -1083,8 +1086,7 @@ int launch_gemm256p(GemmArgs a, int splits, hipStream_t st) {
 bool x6_enabled() { return opt(OPT_GEMM_X6) != 0; }
 
 bool x6_shape_ok(int64_t M, int64_t N, int64_t K) {
-  return x6_enabled() && K % X6_K == 0 && K > 0 && M >= 4 && N >= 4 &&
-         2.0 * (double)M * (double)N * (double)K >= 1.6e10;
+  return x6_enabled() && K % X6_K == 0 && K > 0 && M >= 4 && N >= 4 && big_flops(M, N, K);
 }
 
 int64_t x6_np(int64_t N) { return ceil_div(N, LB_N) * LB_N; }
@@ -1094,23 +1096,13 @@ size_t x6_ws_bytes(int64_t M, int64_t N, int64_t K) {
   return x6_shape_ok(M, N, K) ? (size_t)3 * (size_t)x6_np(N) * (size_t)K * 2 + 256 : 0;
 }
 
-// The path choice for an M-row call made on behalf of `path_rows` rows (a
-// node-range shard's rows of a graph of path_rows nodes; 0: M itself): the
-// size floor is the whole call's, so every shard takes the one-GPU path.
-// (The x6 kernels clamp their A rows, so any M >= 1 is safe on them.)
-bool x6_path_ok(int64_t M, int64_t path_rows, int64_t N, int64_t K) {
-  return M >= 1 && x6_shape_ok(path_rows_of(M, path_rows), N, K);
-}
-size_t x6_ws_bytes_p(int64_t M, int64_t path_rows, int64_t N, int64_t K) {
-  return M >= 1 ? x6_ws_bytes(path_rows_of(M, path_rows), N, K) : 0;
-}
-
+// B (K x N; B_KC: stored [N][K]) into its three bf16 planes
 template <bool B_KC>
-int split_b_planes(const GemmArgs& a, uint16_t* planes, hipStream_t st) {
-  const int64_t Np = x6_np(a.N);
-  const int64_t n_el = Np * a.K;
+int split_b_planes(const float* B, int64_t ldb, int64_t N, int64_t K, uint16_t* planes, hipStream_t st) {
+  const int64_t Np = x6_np(N);
+  const int64_t n_el = Np * K;
   hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n_el, 256), 4096)), dim3(256), 0,
-                     st, a.B, a.ldb, B_KC ? 1 : 0, a.N, a.K, Np, planes);
+                     st, B, ldb, B_KC ? 1 : 0, N, K, Np, planes);
   GRL_LAUNCH_CHECK();
   return GRL_OK;
 }
@@ -1133,10 +1125,37 @@ int launch_x6_gemm(GemmArgs a, const uint16_t* planes, hipStream_t st) {
   return GRL_OK;
 }
 
+}  // namespace
+
+// ---- the x6 GEMM as the GraphConv layer takes it (grl_internal.h) ----------
+// The path choice for an M-row call made on behalf of `path_rows` rows (a
+// node-range shard's rows of a graph of path_rows nodes; 0: M itself): the
+// size floor is the whole call's, so every shard takes the one-GPU path.
+// (The x6 kernels clamp their A rows, so any M >= 1 is safe on them.)
+bool x6_path_ok(int64_t M, int64_t path_rows, int64_t N, int64_t K) {
+  return M >= 1 && x6_shape_ok(path_rows_of(M, path_rows), N, K);
+}
+size_t x6_ws_bytes_p(int64_t M, int64_t path_rows, int64_t N, int64_t K) {
+  return M >= 1 ? x6_ws_bytes(path_rows_of(M, path_rows), N, K) : 0;
+}
+
+int x6_split_w(const float* W, int64_t K, int64_t N, uint16_t* planes, hipStream_t st) {
+  return split_b_planes<false>(W, N, N, K, planes, st);
+}
+int x6_gemm_rows(const float* A, int64_t rows, int64_t K, const uint16_t* planes, int64_t N, const float* bias,
+                 int relu, float* out, hipStream_t st) {
+  GemmArgs a = gemm_args(A, K, nullptr, N, out, N, rows, N, K);
+  a.bias = bias;
+  a.relu = relu;
+  return launch_x6_gemm(a, planes, st);
+}
+
+namespace {
+
 template <bool B_KC>
 int launch_x6(GemmArgs a, void* ws, hipStream_t st) {
   uint16_t* planes = static_cast<uint16_t*>(ws);
-  const int rc = split_b_planes<B_KC>(a, planes, st);
+  const int rc = split_b_planes<B_KC>(a.B, a.ldb, a.N, a.K, planes, st);
   return rc ? rc : launch_x6_gemm(a, planes, st);
 }
 
@@ -1204,6 +1223,10 @@ int run_output_gemm(GemmArgs a, bool aligned, const char* who, void* ws, size_t 
 
 using namespace grl;
 
+extern "C" int32_t grl_linear_fwd_path(int64_t M, int32_t K, int32_t C, int64_t path_rows) {
+  return x6_path_ok(M, path_rows, C, K) ? 1 : 0;
+}
+
 // x6-sized calls need W's planes; the others the fp32 path's slabs (at most kFp32SlabCap)
 extern "C" size_t grl_linear_fwd_ex_workspace_size(int64_t M, int32_t K, int32_t C, int64_t path_rows) {
   if (M <= 0 || K <= 0 || C <= 0) return 0;
@@ -1223,17 +1246,8 @@ extern "C" int grl_linear_fwd_ex(const float* Z, int64_t ldz, const float* W, in
   GRL_CHECK_ARG(w_layout == 0 || w_layout == 1, "grl_linear_fwd: w_layout must be 0 ([K][C]) or 1 ([C][K])");
   if (M == 0 || C == 0) return GRL_OK;
   GRL_CHECK_ARG(Z && W && out, "grl_linear_fwd: NULL pointer");
-  GemmArgs a{};
-  a.A = Z;
-  a.lda = ldz;
-  a.B = W;
-  a.ldb = w_layout ? K : C;
-  a.C = out;
-  a.ldc = C;
+  GemmArgs a = gemm_args(Z, ldz, W, w_layout ? K : C, out, C, M, C, K);
   a.bias = bias;
-  a.M = M;
-  a.N = C;
-  a.K = K;
   a.relu = relu;
   a.path_rows = path_rows;
   const bool aligned = al16(Z) && al16(W) && ldz % 4 == 0 && C % 4 == 0 && K % 4 == 0;
@@ -1248,187 +1262,6 @@ extern "C" int grl_linear_fwd(const float* Z, int64_t ldz, const float* W, const
   return grl_linear_fwd_ex(Z, ldz, W, 0, bias, out, M, K, C, relu, 0, workspace, workspace_bytes, stream);
 }
 
-static size_t ws_align(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// the two-kernel form's workspace for a graph whose GEMM path is chosen for path_rows rows
-static size_t graphconv_two_kernel_ws(const GrlTypedCsr* g, int F, int C) {
-  const int64_t K = (int64_t)(g->num_types + (g->has_self ? 1 : 0)) * F;
-  return ws_align((size_t)g->num_rows * (size_t)K * 4) +
-         grl_linear_fwd_ex_workspace_size(g->num_rows, (int32_t)K, C, g->path_rows);
-}
-
-// grl_graphconv_fwd takes the fused kernel when its arithmetic equals the
-// two-kernel path's (the linear on the x6 GEMM: large graphs, 16-B aligned W,
-// C % 4 == 0), the shapes fit it (F in {64, 128, 256, 512, 1024}, C <= 512), X rows are
-// float4-aligned and no heavy row is split (the split path sums chunk
-// partials, a different order).
-static bool fused_path(const GrlTypedCsr* g, const float* X, int64_t ldx, int F, const float* W, int C) {
-  const int64_t K = (int64_t)(g->num_types + (g->has_self ? 1 : 0)) * F;
-  return graphconv_fused_enabled() && graphconv_fused_shape_ok(F, C, g->num_types) &&
-         x6_path_ok(g->num_rows, g->path_rows, C, K) &&
-         al16(W) && C % 4 == 0 && al16(X) && ldx % 4 == 0 && ldx < (1LL << 30) &&  // gather: 32-bit row bytes
-         (!g->split || g->split->num_heavy == 0);
-}
-
-extern "C" size_t grl_graphconv_fwd_workspace_query(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F,
-                                                   const float* W, int32_t C) {
-  if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0) return 0;
-  const int64_t K = (int64_t)(g->num_types + (g->has_self ? 1 : 0)) * F;
-  if (K > 2147483647LL) return 0;
-  if (fused_path(g, X, ldx, F, W, C)) return graphconv_fused_ws_bytes(K, C);
-  return graphconv_two_kernel_ws(g, F, C);
-}
-
-extern "C" size_t grl_graphconv_fwd_workspace_size(int64_t num_rows, int32_t num_types, int32_t has_self, int32_t F,
-                                                   int32_t C) {
-  if (num_rows <= 0 || num_types < 1 || F <= 0 || C <= 0) return 0;
-  const int64_t K = (int64_t)(num_types + (has_self ? 1 : 0)) * F;
-  if (K > 2147483647LL) return 0;
-  return ws_align((size_t)num_rows * (size_t)K * 4) + grl_linear_fwd_workspace_size(num_rows, (int32_t)K, C);
-}
-
-
-extern "C" int grl_graphconv_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
-                                 const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
-                                 void* workspace, size_t workspace_bytes, grl_stream_t stream) {
-  TraceRange trace_("grl_graphconv_fwd");
-  GRL_CHECK_ARG(g != nullptr, "grl_graphconv_fwd: graph is NULL");
-  GRL_CHECK_ARG(g->num_rows >= 0 && g->num_types >= 1 && g->num_types <= 63,
-                "grl_graphconv_fwd: num_types must be in [1, 63] (got %d)", g->num_types);
-  GRL_CHECK_ARG(F > 0 && ldx >= F && C > 0, "grl_graphconv_fwd: need F > 0, ldx >= F, C > 0");
-  const int64_t M = g->num_rows;
-  if (M == 0) return GRL_OK;
-  GRL_CHECK_ARG(X && W && out && g->rowptr && (g->nnz == 0 || g->colidx), "grl_graphconv_fwd: NULL pointer");
-  const int hs = g->has_self ? 1 : 0;
-  const int64_t K64 = (int64_t)(g->num_types + hs) * F;
-  GRL_CHECK_ARG(K64 <= 2147483647LL, "grl_graphconv_fwd: (has_self + num_types) * F exceeds int32");
-  const int32_t K = (int32_t)K64;
-  hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  GRL_CHECK_ARG(ws == nullptr || al16(ws), "grl_graphconv_fwd: workspace must be 16-B aligned");
-  const size_t zfull = ws_align((size_t)M * (size_t)K * 4);
-  if (fused_path(g, X, ldx, F, W, C) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C)) {
-    // one kernel: Z never leaves the CU (graphconv.hip)
-    GRL_CHECK_ARG(g->nnz < 2147483647LL, "grl_graphconv_fwd: nnz %lld exceeds int32", (long long)g->nnz);
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, ws, st);
-  }
-  if (ws && workspace_bytes >= graphconv_two_kernel_ws(g, F, C)) {
-    // whole graph: Z in the workspace, then the linear (its workspace behind Z)
-    float* Z = reinterpret_cast<float*>(ws);
-    int rc = grl_typed_spmm_fwd(g, X, ldx, F, Z, de, stream);
-    if (rc) return rc;
-    return grl_linear_fwd_ex(Z, K, W, 0, bias, out, M, K, C, relu, g->path_rows, ws + zfull, workspace_bytes - zfull,
-                             stream);
-  }
-  // Row chunks: Z for R rows at a time (bounded memory), on the x6 GEMM only,
-  // whose per-element arithmetic does not depend on M -- so the result is
-  // bitwise that of the whole-graph call.
-  const bool x6 = x6_path_ok(M, g->path_rows, C, K) && al16(W) && C % 4 == 0;
-  if (!x6 || (g->split && g->split->num_heavy > 0) || !ws)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_fwd: workspace %zu < %zu (row chunking needs the x6 GEMM shape and no "
-             "heavy-row split plan)", workspace_bytes, grl_graphconv_fwd_workspace_size(M, g->num_types, hs, F, C));
-  const size_t planes_bytes = ws_align(x6_ws_bytes_p(M, g->path_rows, C, K));
-  const int64_t per_row = (int64_t)K * 4;
-  int64_t R = workspace_bytes > planes_bytes ? (int64_t)((workspace_bytes - planes_bytes) / per_row) : 0;
-  R = R / LB_M * LB_M;
-  if (R < LB_M)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_fwd: workspace %zu holds fewer than %d rows of Z", workspace_bytes, LB_M);
-  uint16_t* planes = reinterpret_cast<uint16_t*>(ws);
-  float* Z = reinterpret_cast<float*>(ws + planes_bytes);
-  GemmArgs a{};
-  a.B = W;
-  a.ldb = C;
-  a.N = C;
-  a.K = K;
-  a.bias = bias;
-  a.relu = relu;
-  a.lda = K;
-  a.ldc = C;
-  int rc = split_b_planes<false>(a, planes, st);
-  if (rc) return rc;
-  for (int64_t r0 = 0; r0 < M; r0 += R) {
-    const int64_t rows = std::min<int64_t>(R, M - r0);
-    rc = spmm_fwd_rows(g, r0, rows, X, ldx, F, Z, de, st);
-    if (rc) return rc;
-    a.A = Z;
-    a.M = rows;
-    a.C = out + r0 * C;
-    rc = launch_x6_gemm(a, planes, st);
-    if (rc) return rc;
-  }
-  return GRL_OK;
-}
-
-// The data gradient of one GraphConv layer by reassociation (see grl.h):
-// dX = sum_s (A_drop,s^T G) W_s^T on the one-kernel GraphConv over the typed
-// transpose.  Eligible when the forward's x6 GEMM shape would be (large
-// graphs), C in {64, 128, 256, 512, 1024}, F <= 512, L <= 7, G rows float4-aligned and no
-// heavy-row split plan on the transpose.
-static bool bwd_data_path(const GrlTypedCsr* gt, const float* G, int64_t ldg, int C, const float* W, int F) {
-  const int64_t K = (int64_t)(gt->num_types + (gt->has_self ? 1 : 0)) * C;
-  return gt->self_row0 == 0 && graphconv_fused_enabled() && graphconv_fused_shape_ok(C, F, gt->num_types) && x6_shape_ok(gt->num_rows, F, K) &&
-         al16(W) && F % 4 == 0 && al16(G) && ldg % 4 == 0 && ldg < (1LL << 30) &&
-         (!gt->split || gt->split->num_heavy == 0) &&
-         K <= 2147483647LL && gt->nnz < 2147483647LL;
-}
-
-extern "C" size_t grl_graphconv_bwd_data_workspace_query(const GrlTypedCsr* gt, const float* G, int64_t ldg, int32_t C,
-                                                        const float* W, int32_t F) {
-  if (!gt || gt->num_rows <= 0 || gt->num_types < 1 || C <= 0 || F <= 0) return 0;
-  if (!bwd_data_path(gt, G, ldg, C, W, F)) return 0;
-  return graphconv_fused_ws_bytes((int64_t)(gt->num_types + (gt->has_self ? 1 : 0)) * C, F);
-}
-
-extern "C" int grl_graphconv_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const float* G, int64_t ldg,
-                                      int64_t g_rows, int32_t C, const float* W, int32_t F, float* dX, float* G_agg,
-                                      const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
-                                      grl_stream_t stream) {
-  TraceRange trace_("grl_graphconv_bwd_data");
-  GRL_CHECK_ARG(gt != nullptr, "grl_graphconv_bwd_data: graph is NULL");
-  GRL_CHECK_ARG(gt->num_rows >= 0 && gt->num_types >= 1 && gt->num_types <= 63,
-                "grl_graphconv_bwd_data: num_types must be in [1, 63] (got %d)", gt->num_types);
-  GRL_CHECK_ARG(C > 0 && ldg >= C && F > 0 && g_rows >= 0 && g_rows <= gt->num_rows,
-                "grl_graphconv_bwd_data: need C > 0, ldg >= C, F > 0, 0 <= g_rows <= num_rows");
-  if (gt->num_rows == 0) return GRL_OK;
-  // (an empty node-range shard: no G rows and no entries, so its empty G is never read)
-  GRL_CHECK_ARG((G || (g_rows == 0 && gt->nnz == 0)) && W && dX && gt->rowptr && (gt->nnz == 0 || (gt->colidx && eid)),
-                "grl_graphconv_bwd_data: NULL pointer");
-  if (!bwd_data_path(gt, G, ldg, C, W, F))
-    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_graphconv_bwd_data: shape outside the one-kernel path (C %d, F %d, L %d, rows "
-             "%lld; see grl_graphconv_bwd_data_workspace_query)", C, F, gt->num_types, (long long)gt->num_rows);
-  const size_t need = graphconv_fused_ws_bytes((int64_t)(gt->num_types + (gt->has_self ? 1 : 0)) * C, F);
-  if (!workspace || !al16(workspace) || workspace_bytes < need)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_bwd_data: workspace %zu < %zu (16-B aligned)", workspace_bytes, need);
-  return graphconv_fused_bwd_data(gt, eid, G, ldg, g_rows, C, W, F, dX, G_agg, de, workspace, as_stream(stream));
-}
-
-extern "C" int grl_graphconv_fwd_train(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
-                                       const float* bias, int32_t C, int32_t relu, float* out, float* Z,
-                                       const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
-                                       grl_stream_t stream) {
-  TraceRange trace_("grl_graphconv_fwd_train");
-  GRL_CHECK_ARG(g != nullptr, "grl_graphconv_fwd_train: graph is NULL");
-  GRL_CHECK_ARG(g->num_rows >= 0 && g->num_types >= 1 && g->num_types <= 63,
-                "grl_graphconv_fwd_train: num_types must be in [1, 63] (got %d)", g->num_types);
-  GRL_CHECK_ARG(F > 0 && ldx >= F && C > 0, "grl_graphconv_fwd_train: need F > 0, ldx >= F, C > 0");
-  const int64_t M = g->num_rows;
-  if (M == 0) return GRL_OK;
-  GRL_CHECK_ARG(X && W && out && Z && g->rowptr && (g->nnz == 0 || g->colidx), "grl_graphconv_fwd_train: NULL pointer");
-  const int hs = g->has_self ? 1 : 0;
-  const int64_t K64 = (int64_t)(g->num_types + hs) * F;
-  GRL_CHECK_ARG(K64 <= 2147483647LL, "grl_graphconv_fwd_train: (has_self + num_types) * F exceeds int32");
-  const int32_t K = (int32_t)K64;
-  char* ws = static_cast<char*>(workspace);
-  GRL_CHECK_ARG(ws == nullptr || al16(ws), "grl_graphconv_fwd_train: workspace must be 16-B aligned");
-  if (fused_path(g, X, ldx, F, W, C) && al16(Z) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C)) {
-    GRL_CHECK_ARG(g->nnz < 2147483647LL, "grl_graphconv_fwd_train: nnz %lld exceeds int32", (long long)g->nnz);
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, ws, as_stream(stream), Z);
-  }
-  const int rc = grl_typed_spmm_fwd(g, X, ldx, F, Z, de, stream);
-  return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, M, K, C, relu, g->path_rows, workspace, workspace_bytes,
-                                     stream);
-}
-
 extern "C" size_t grl_linear_bwd_data_workspace_size(int64_t M, int32_t K, int32_t C) {
   if (M <= 0 || K <= 0 || C <= 0) return 0;
   return x6_shape_ok(M, K, C) ? x6_ws_bytes(M, K, C) : small_ws_bytes(M, 0, K, C);
@@ -1441,17 +1274,9 @@ extern "C" int grl_linear_bwd_data(const float* g, const float* relu_out, const 
   GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0 && lddz >= K, "grl_linear_bwd_data: bad sizes");
   if (M == 0 || K == 0) return GRL_OK;
   GRL_CHECK_ARG(g && W && dZ, "grl_linear_bwd_data: NULL pointer");
-  GemmArgs a{};
-  a.A = g;  // (M x C), k index = c contiguous
-  a.lda = C;
+  // A = g (M x C), k index = c contiguous; B(k=c, n=kk) = W[kk][c]: K-contiguous rows of W
+  GemmArgs a = gemm_args(g, C, W, C, dZ, lddz, M, K, C);
   a.Amask = relu_out;
-  a.B = W;  // B(k=c, n=kk) = W[kk][c]: K-contiguous rows of W
-  a.ldb = C;
-  a.C = dZ;
-  a.ldc = lddz;
-  a.M = M;
-  a.N = K;
-  a.K = C;
   const bool aligned = al16(g) && al16(W) && (!relu_out || al16(relu_out)) && C % 4 == 0;
   return run_output_gemm<true, true>(a, aligned, "grl_linear_bwd_data", workspace, workspace_bytes,
                                      as_stream(stream));
@@ -1461,8 +1286,7 @@ namespace grl {
 namespace {
 // x6t (split-bf16 dW) selection: same switch and size floor as the forward
 bool x6t_shape_ok(int64_t M, int64_t K, int64_t C) {  // M nodes, K = rows of dW, C = its columns
-  return x6_enabled() && M >= 16 && K >= 4 && C >= 4 && K % 4 == 0 && C % 4 == 0 &&
-         2.0 * (double)M * (double)K * (double)C >= 1.6e10;
+  return x6_enabled() && M >= 16 && K >= 4 && C >= 4 && K % 4 == 0 && C % 4 == 0 && big_flops(M, K, C);
 }
 
 // K splits of the x6t dW: at most two 256 x 256 workgroups per CU (one is
@@ -1548,16 +1372,9 @@ extern "C" int grl_linear_bwd_weight(const float* Z, int64_t ldz, const float* g
     GRL_FAIL(GRL_E_WORKSPACE, "grl_linear_bwd_weight: workspace %zu < %zu", workspace_bytes, need);
   hipStream_t st = as_stream(stream);
   float* slab = static_cast<float*>(workspace);
-  GemmArgs a{};
-  a.A = Z;  // A(m=kk, k=row) = Z[row][kk]: rows of Z are M-contiguous for fixed k
-  a.lda = ldz;
-  a.B = g;  // B(k=row, n=c) = g[row][c]
-  a.ldb = C;
+  // A(m=kk, k=row) = Z[row][kk]: rows of Z are M-contiguous for fixed k; B(k=row, n=c) = g[row][c]; C set below
+  GemmArgs a = gemm_args(Z, ldz, g, C, nullptr, C, K, C, M);
   a.Bmask = relu_out;
-  a.ldc = C;
-  a.M = K;
-  a.N = C;
-  a.K = M;
   const bool aligned = al16(Z) && al16(g) && (!relu_out || al16(relu_out)) && ldz % 4 == 0 && C % 4 == 0 && K % 4 == 0;
   int used;
   if (aligned && !relu_out && x6t_shape_ok(M, K, C)) {  // large M: fp32 on the bf16 matrix cores

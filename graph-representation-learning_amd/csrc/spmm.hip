@@ -89,7 +89,6 @@ __device__ __forceinline__ void vstore(float* p, const float& v) {
 #endif
 }
 
-
 // Whole-row (F <= 256) gathers in flight per wave (A/B builds: -DGRL_SPMM_U=n).
 #ifndef GRL_SPMM_U
 #define GRL_SPMM_U 8
@@ -681,15 +680,27 @@ int launch_spmm(int64_t num_rows, int64_t self_rows, int S, int hs, const int32_
 
 }  // namespace
 
+int csr_fwd_check(const char* who, const GrlTypedCsr* g, int F, int64_t ldx, bool ptrs) {
+  GRL_CHECK_ARG(g != nullptr, "%s: graph is NULL", who);
+  GRL_CHECK_ARG(g->num_rows >= 0 && g->num_types >= 1 && g->num_types <= 63,
+                "%s: num_types must be in [1, 63] (got %d)", who, g->num_types);
+  GRL_CHECK_ARG(F > 0 && ldx >= F, "%s: need F > 0 and ldx >= F (F=%d ldx=%lld)", who, F, (long long)ldx);
+  if (g->num_rows == 0) return GRL_OK;
+  GRL_CHECK_ARG(ptrs && g->rowptr && (g->nnz == 0 || g->colidx), "%s: NULL pointer", who);
+  GRL_CHECK_ARG(g->nnz < 2147483647LL, "%s: nnz %lld exceeds int32", who, (long long)g->nnz);
+  GRL_CHECK_ARG(g->self_row0 >= 0, "%s: negative self_row0", who);
+  return GRL_OK;
+}
+
 // Z rows [0, rows) = rows [r0, r0 + rows) of A_drop X (grl_graphconv_fwd's
 // row chunks): rowptr offset by r0 rows (edge positions, hence edge ids, stay
 // absolute), self term X row and self id shifted by r0.  Per row identical to
 // the whole-graph launch; no split plan (the caller checks).
 int spmm_fwd_rows(const GrlTypedCsr* g, int64_t r0, int64_t rows, const float* X, int64_t ldx, int F, float* Z,
                   const GrlDropEdge* de, hipStream_t st) {
-  const int hs = g->has_self ? 1 : 0;
-  const int64_t ldz = (int64_t)(g->num_types + hs) * F;
-  return launch_spmm<false>(rows, rows, g->num_types, hs, g->rowptr + r0 * g->num_types, g->colidx, nullptr, g->vals,
+  const int64_t ldz = (int64_t)segments(g) * F;
+  return launch_spmm<false>(rows, rows, g->num_types, g->has_self ? 1 : 0, g->rowptr + r0 * g->num_types, g->colidx,
+                            nullptr, g->vals,
                             g->edge_id_base, g->self_id_base + (uint64_t)r0, X, ldx, F, Z, ldz, to_dev(de), nullptr,
                             st, Z, g->self_row0 + r0, g->num_rows);
 }
@@ -751,43 +762,29 @@ extern "C" int grl_dropedge_mask(const GrlDropEdge* de, uint64_t id_base, int64_
 extern "C" int grl_typed_spmm_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, float* Z,
                                   const GrlDropEdge* de, grl_stream_t stream) {
   TraceRange trace_("grl_typed_spmm_fwd");
-  GRL_CHECK_ARG(g != nullptr, "grl_typed_spmm_fwd: graph is NULL");
-  GRL_CHECK_ARG(g->num_rows >= 0 && g->num_types >= 1 && g->num_types <= 63,
-                "grl_typed_spmm_fwd: num_types must be in [1, 63] (got %d)", g->num_types);
-  GRL_CHECK_ARG(F > 0 && ldx >= F, "grl_typed_spmm_fwd: need F > 0 and ldx >= F (F=%d ldx=%lld)", F,
-                (long long)ldx);
-  if (g->num_rows == 0) return GRL_OK;
-  GRL_CHECK_ARG(X && Z && g->rowptr && (g->nnz == 0 || g->colidx), "grl_typed_spmm_fwd: NULL pointer");
-  GRL_CHECK_ARG(g->nnz < 2147483647LL, "grl_typed_spmm_fwd: nnz %lld exceeds int32", (long long)g->nnz);
-  GRL_CHECK_ARG(g->self_row0 >= 0, "grl_typed_spmm_fwd: negative self_row0");
-  const int hs = g->has_self ? 1 : 0;
-  const int64_t ldz = (int64_t)(g->num_types + hs) * F;
-  return launch_spmm<false>(g->num_rows, g->num_rows, g->num_types, hs, g->rowptr, g->colidx, nullptr, g->vals,
-                            g->edge_id_base, g->self_id_base, X, ldx, F, Z, ldz, to_dev(de), g->split,
-                            as_stream(stream), Z, g->self_row0);
+  const int rc = csr_fwd_check("grl_typed_spmm_fwd", g, F, ldx, X && Z);
+  if (rc || g->num_rows == 0) return rc;
+  const int64_t ldz = (int64_t)segments(g) * F;
+  return launch_spmm<false>(g->num_rows, g->num_rows, g->num_types, g->has_self ? 1 : 0, g->rowptr, g->colidx,
+                            nullptr, g->vals, g->edge_id_base, g->self_id_base, X, ldx, F, Z, ldz, to_dev(de),
+                            g->split, as_stream(stream), Z, g->self_row0);
 }
 
 extern "C" int grl_typed_spmm_fwd_slice(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F,
                                         int64_t self_col0, float* Z, int64_t ldz, int32_t zseg,
                                         const GrlDropEdge* de, grl_stream_t stream) {
   TraceRange trace_("grl_typed_spmm_fwd_slice");
-  GRL_CHECK_ARG(g != nullptr, "grl_typed_spmm_fwd_slice: graph is NULL");
-  GRL_CHECK_ARG(g->num_rows >= 0 && g->num_types >= 1 && g->num_types <= 63,
-                "grl_typed_spmm_fwd_slice: num_types must be in [1, 63] (got %d)", g->num_types);
-  GRL_CHECK_ARG(F > 0 && ldx >= F && zseg >= F && self_col0 >= 0,
-                "grl_typed_spmm_fwd_slice: need F > 0, ldx >= F, zseg >= F, self_col0 >= 0 (F=%d ldx=%lld zseg=%d)",
-                F, (long long)ldx, zseg, (long long)self_col0);
-  const int hs = g->has_self ? 1 : 0;
-  GRL_CHECK_ARG(ldz >= (int64_t)(g->num_types + hs - 1) * zseg + F,
+  const int rc = csr_fwd_check("grl_typed_spmm_fwd_slice", g, F, ldx, X && Z);
+  if (rc) return rc;
+  GRL_CHECK_ARG(zseg >= F && self_col0 >= 0, "grl_typed_spmm_fwd_slice: need zseg >= F, self_col0 >= 0 (zseg=%d "
+                "self_col0=%lld)", zseg, (long long)self_col0);
+  GRL_CHECK_ARG(ldz >= (int64_t)(segments(g) - 1) * zseg + F,
                 "grl_typed_spmm_fwd_slice: ldz %lld too small for %d segments of stride %d", (long long)ldz,
-                g->num_types + hs, zseg);
+                segments(g), zseg);
   if (g->num_rows == 0) return GRL_OK;
-  GRL_CHECK_ARG(X && Z && g->rowptr && (g->nnz == 0 || g->colidx), "grl_typed_spmm_fwd_slice: NULL pointer");
-  GRL_CHECK_ARG(g->nnz < 2147483647LL, "grl_typed_spmm_fwd_slice: nnz %lld exceeds int32", (long long)g->nnz);
-  GRL_CHECK_ARG(g->self_row0 >= 0, "grl_typed_spmm_fwd_slice: negative self_row0");
-  return launch_spmm<false>(g->num_rows, g->num_rows, g->num_types, hs, g->rowptr, g->colidx, nullptr, g->vals,
-                            g->edge_id_base, g->self_id_base, X, ldx, F, Z, ldz, to_dev(de), g->split,
-                            as_stream(stream), Z, self_col0 + g->self_row0, -1, zseg);
+  return launch_spmm<false>(g->num_rows, g->num_rows, g->num_types, g->has_self ? 1 : 0, g->rowptr, g->colidx,
+                            nullptr, g->vals, g->edge_id_base, g->self_id_base, X, ldx, F, Z, ldz, to_dev(de),
+                            g->split, as_stream(stream), Z, self_col0 + g->self_row0, -1, zseg);
 }
 
 // dX columns [0, F) = columns [col0, col0 + F) of A_drop^T dZ, dZ segments

@@ -150,12 +150,14 @@ SIGNATURES = {
     "grl_graphconv_bwd_data_workspace_query": (_c_size, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_i32]),
     "grl_graphconv_bwd_data": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_vp, _c_i32,
                                         _c_vp, _c_vp, _P(GrlDropEdge), _c_vp, _c_size, _c_vp]),
+    "grl_graphconv_bwd_data_shape_ok": (_c_i32, [_c_i64, _c_i32, _c_i32, _c_i32, _c_i32]),
     "grl_graphconv_fwd": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i32, _c_i32, _c_vp,
                                    _P(GrlDropEdge), _c_vp, _c_size, _c_vp]),
     "grl_linear_fwd_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32]),
     "grl_linear_fwd": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_vp, _c_size,
                                 _c_vp]),
     "grl_linear_fwd_ex_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32, _c_i64]),
+    "grl_linear_fwd_path": (_c_i32, [_c_i64, _c_i32, _c_i32, _c_i64]),
     "grl_linear_fwd_ex": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i32, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_i64,
                                    _c_vp, _c_size, _c_vp]),
     "grl_linear_bwd_data_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32]),

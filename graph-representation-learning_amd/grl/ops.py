@@ -27,29 +27,64 @@ def _rows_view(X: torch.Tensor) -> torch.Tensor:
     return X2
 
 
+def _ptr(t):
+    """A tensor's address, or None (NULL) for no tensor."""
+    return t.data_ptr() if t is not None else None
+
+
+def _workspace(nbytes: int, device):
+    """A workspace of nbytes on `device`; None (NULL) for none."""
+    return torch.empty(nbytes, dtype=torch.uint8, device=device) if nbytes else None
+
+
+def _de_ref(graph):
+    """The graph's DropEdge record by reference, or None (NULL) without one.
+    The reference holds the ctypes struct, which so lives as long as the
+    call's argument list."""
+    return ctypes.byref(graph.dropedge.to_c()) if graph.dropedge is not None else None
+
+
+def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: bool = False):
+    """The checked operands of a forward over `graph` -- (X2, F, Wc, bc, out,
+    Z): the features' 2-D row view and width, the contiguous weights
+    [segments * F, C] and bias (None without), out [num_rows, C] (with
+    weights) and Z [num_rows, segments * F] (want_Z), each the contiguous
+    fp32 tensor given or a new one."""
+    _require_device(X, "node features")
+    if W is None and X.dtype != torch.float32:
+        raise _lib.GrlError(f"node features must be float32 (got {X.dtype})")
+    if W is not None and (X.dtype != torch.float32 or W.dtype != torch.float32):
+        raise _lib.GrlError(f"{who}: features and weights must be float32")
+    X2 = _rows_view(X)
+    if X2.shape[0] != graph.num_cols:
+        raise _lib.GrlError(f"features have {X2.shape[0]} rows, graph gathers from {graph.num_cols}")
+    F = X2.shape[1]
+    K = graph.segments * F
+    Wc = W.contiguous() if W is not None else None
+    if Wc is not None and Wc.shape[0] != K:
+        raise _lib.GrlError(f"weights have {Wc.shape[0]} rows, expected {graph.segments} x {F}")
+
+    def target(t, what, cols):
+        shape = (graph.num_rows, cols)
+        if t is None:
+            return torch.empty(shape, dtype=torch.float32, device=X.device)
+        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != X.device:
+            raise _lib.GrlError(f"{who}: {what} must be a contiguous float32 {shape} tensor on {X.device}")
+        return t
+
+    return (X2, F, Wc, b.contiguous() if b is not None else None,
+            target(out, "out", Wc.shape[1]) if Wc is not None else None, target(Z, "Z", K) if want_Z else None)
+
+
 def spmm_forward(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor = None) -> torch.Tensor:
     """Z = A_drop X without autograd bookkeeping, optionally into `out`
     (contiguous [num_rows, segments*F] fp32): the inference / benchmark form."""
     if isinstance(graph, EdgeBlockedGraph):
         return _blocked_forward(X, graph, out)
-    _require_device(X, "node features")
-    if X.dtype != torch.float32:
-        raise _lib.GrlError(f"node features must be float32 (got {X.dtype})")
-    X2 = _rows_view(X)
-    if X2.shape[0] != graph.num_cols:
-        raise _lib.GrlError(f"features have {X2.shape[0]} rows, graph gathers from {graph.num_cols}")
-    F = X2.shape[1]
-    shape = (graph.num_rows, graph.segments * F)
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=X.device)
-    elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous() \
-            or out.device != X.device:
-        raise _lib.GrlError(f"out must be a contiguous float32 {shape} tensor on {X.device}")
-    csr = graph.csr_c(F)
-    de = graph.dropedge.to_c() if graph.dropedge is not None else None
-    call("grl_typed_spmm_fwd", ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, out.data_ptr(),
-         ctypes.byref(de) if de is not None else None, current_stream_handle(X.device))
-    return out
+    X2, F, _, _, _, Z = _forward_args("spmm_forward", X, graph, Z=out, want_Z=True)
+    call("grl_typed_spmm_fwd", ctypes.byref(graph.csr_c(F)), X2.data_ptr(), X2.stride(0), F, Z.data_ptr(),
+         _de_ref(graph), current_stream_handle(X.device))
+    return Z
 
 
 def spmm_forward_slice(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor, col0: int,
@@ -73,11 +108,8 @@ def spmm_forward_slice(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor, co
     zseg = out.shape[1] // S
     if col0 < 0 or col0 + F > zseg:
         raise _lib.GrlError(f"columns [{col0}, {col0 + F}) outside the {zseg}-column segments")
-    csr = graph.csr_c(F)
-    de = graph.dropedge.to_c() if graph.dropedge is not None else None
-    call("grl_typed_spmm_fwd_slice", ctypes.byref(csr), X.data_ptr(), X.stride(0), F, int(self_col0),
-         out.data_ptr() + 4 * col0, out.stride(0), zseg, ctypes.byref(de) if de is not None else None,
-         current_stream_handle(X.device))
+    call("grl_typed_spmm_fwd_slice", ctypes.byref(graph.csr_c(F)), X.data_ptr(), X.stride(0), F, int(self_col0),
+         out.data_ptr() + 4 * col0, out.stride(0), zseg, _de_ref(graph), current_stream_handle(X.device))
     return out
 
 
@@ -110,9 +142,8 @@ def _blocked_backward(dZ: torch.Tensor, graph: EdgeBlockedGraph, F: int) -> torc
         csc = blk.csc_c(F)
         if i == 0:
             csc.self_rows = min(graph.num_rows, graph.num_cols)  # every node's self loop, dZ rows from 0
-        de = blk.dropedge.to_c() if blk.dropedge is not None else None
         call("grl_typed_spmm_bwd" if i == 0 else "grl_typed_spmm_bwd_accum", ctypes.byref(csc),
-             dZ.data_ptr() + 4 * r0 * ldz, F, dX.data_ptr(), F, ctypes.byref(de) if de is not None else None, stream)
+             dZ.data_ptr() + 4 * r0 * ldz, F, dX.data_ptr(), F, _de_ref(blk), stream)
     return dX
 
 
@@ -122,10 +153,8 @@ def spmm_backward(dZ: torch.Tensor, graph: TypedGraph, F: int) -> torch.Tensor:
         return _blocked_backward(dZ, graph, F)
     dZ = dZ.contiguous().float()
     dX = torch.empty(graph.num_cols, F, dtype=torch.float32, device=dZ.device)
-    csc = graph.csc_c(F)
-    de = graph.dropedge.to_c() if graph.dropedge is not None else None
-    call("grl_typed_spmm_bwd", ctypes.byref(csc), dZ.data_ptr(), F, dX.data_ptr(), F,
-         ctypes.byref(de) if de is not None else None, current_stream_handle(dZ.device))
+    call("grl_typed_spmm_bwd", ctypes.byref(graph.csc_c(F)), dZ.data_ptr(), F, dX.data_ptr(), F, _de_ref(graph),
+         current_stream_handle(dZ.device))
     return dX
 
 
@@ -146,10 +175,8 @@ def spmm_backward_slice(dZ: torch.Tensor, graph: TypedGraph, col0: int, out: tor
             or out.device != dZ.device:
         raise _lib.GrlError(f"out must be a float32 [{graph.num_cols}, F] tensor with unit column stride")
     F = out.shape[1]
-    csc = graph.csc_c(F)
-    de = graph.dropedge.to_c() if graph.dropedge is not None else None
-    call("grl_typed_spmm_bwd_slice", ctypes.byref(csc), dZ.data_ptr(), F_total, int(col0), F, out.data_ptr(),
-         out.stride(0), ctypes.byref(de) if de is not None else None, current_stream_handle(dZ.device))
+    call("grl_typed_spmm_bwd_slice", ctypes.byref(graph.csc_c(F)), dZ.data_ptr(), F_total, int(col0), F,
+         out.data_ptr(), out.stride(0), _de_ref(graph), current_stream_handle(dZ.device))
     return out
 
 
@@ -197,9 +224,9 @@ def relu_grad(g: torch.Tensor, out, want_db: bool = False):
     g_eff = torch.empty_like(g)
     db = torch.empty(C, dtype=torch.float32, device=g.device) if want_db else None
     ws_bytes = _lib.lib().grl_relu_grad_workspace_size(M, C) if want_db else 0
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device) if ws_bytes else None
-    call("grl_relu_grad", g.data_ptr(), out.data_ptr(), g_eff.data_ptr(), db.data_ptr() if db is not None else None,
-         M, C, ws.data_ptr() if ws is not None else None, ws_bytes, current_stream_handle(g.device))
+    ws = _workspace(ws_bytes, g.device)
+    call("grl_relu_grad", g.data_ptr(), out.data_ptr(), g_eff.data_ptr(), _ptr(db), M, C, _ptr(ws), ws_bytes,
+         current_stream_handle(g.device))
     return g_eff, None, db
 
 
@@ -208,10 +235,9 @@ def linear_fwd(Z2: torch.Tensor, W: torch.Tensor, b, relu: bool) -> torch.Tensor
     C = W.shape[1]
     out = torch.empty(M, C, dtype=torch.float32, device=Z2.device)
     ws_bytes = _lib.lib().grl_linear_fwd_workspace_size(M, K, C)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=Z2.device) if ws_bytes else None
-    call("grl_linear_fwd", Z2.data_ptr(), Z2.stride(0), W.data_ptr(), b.data_ptr() if b is not None else None,
-         out.data_ptr(), M, K, C, int(relu), ws.data_ptr() if ws is not None else None, ws_bytes,
-         current_stream_handle(Z2.device))
+    ws = _workspace(ws_bytes, Z2.device)
+    call("grl_linear_fwd", Z2.data_ptr(), Z2.stride(0), W.data_ptr(), _ptr(b), out.data_ptr(), M, K, C, int(relu),
+         _ptr(ws), ws_bytes, current_stream_handle(Z2.device))
     return out
 
 
@@ -220,10 +246,9 @@ def linear_bwd_data(g: torch.Tensor, relu_out, W: torch.Tensor) -> torch.Tensor:
     K = W.shape[0]
     dZ = torch.empty(M, K, dtype=torch.float32, device=g.device)
     ws_bytes = _lib.lib().grl_linear_bwd_data_workspace_size(M, K, C)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device) if ws_bytes else None
-    call("grl_linear_bwd_data", g.data_ptr(), relu_out.data_ptr() if relu_out is not None else None, W.data_ptr(),
-         dZ.data_ptr(), K, M, K, C, ws.data_ptr() if ws is not None else None, ws_bytes,
-         current_stream_handle(g.device))
+    ws = _workspace(ws_bytes, g.device)
+    call("grl_linear_bwd_data", g.data_ptr(), _ptr(relu_out), W.data_ptr(), dZ.data_ptr(), K, M, K, C, _ptr(ws),
+         ws_bytes, current_stream_handle(g.device))
     return dZ
 
 
@@ -233,11 +258,9 @@ def linear_bwd_weight(Z2: torch.Tensor, g: torch.Tensor, relu_out, want_db: bool
     dW = torch.empty(K, C, dtype=torch.float32, device=g.device)
     db = torch.empty(C, dtype=torch.float32, device=g.device) if want_db else None
     ws_bytes = _lib.lib().grl_linear_bwd_weight_workspace_size(M, K, C)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device)
-    call("grl_linear_bwd_weight", Z2.data_ptr(), Z2.stride(0), g.data_ptr(),
-         relu_out.data_ptr() if relu_out is not None else None, dW.data_ptr(),
-         db.data_ptr() if db is not None else None, M, K, C, ws.data_ptr(), ws_bytes,
-         current_stream_handle(g.device))
+    ws = _workspace(ws_bytes, g.device)
+    call("grl_linear_bwd_weight", Z2.data_ptr(), Z2.stride(0), g.data_ptr(), _ptr(relu_out), dW.data_ptr(), _ptr(db),
+         M, K, C, _ptr(ws), ws_bytes, current_stream_handle(g.device))
     return dW, db
 
 
@@ -273,28 +296,41 @@ class _GraphLinear(torch.autograd.Function):
         return dZ, dW, db_pre if db_pre is not None else db, None, None
 
 
-# Widths of the one-kernel GraphConv (graphconv.hip): the gathered width (the
-# forward's F, or the data gradient's C) and the largest output width of one
-# call (the forward's C, or the data gradient's F; wider dX runs in column
-# blocks).
-FUSED_WIDTHS = (64, 128, 256, 512, 1024)
+# The widest dX one grl_graphconv_bwd_data call writes (the library's rule,
+# grl_graphconv_bwd_data_shape_ok; tests/test_abi.py ties the two): a wider
+# dX runs in column blocks, which this constant cuts.
 FUSED_MAX_OUT = 512
 
 
 def x6_rows_ok(M: int, N: int, K: int, path_rows: int = 0) -> bool:
     """Whether an [M, K] x [K, N] product, chosen for max(M, path_rows) rows,
     takes the split-bf16 GEMM (and so a GraphConv the one-kernel forms): the
-    size rule of x6_path_ok (csrc/linear.hip).  Both GEMM paths' per-element
+    library's own answer (grl_linear_fwd_path).  Both GEMM paths' per-element
     arithmetic is independent of M (the fp32 one sums K in fixed chunks), so
     row blocks of one layer match the whole call bitwise when both take the
     same path -- which path_rows (the whole call's rows) guarantees."""
-    rows = max(M, path_rows)
-    return (_lib.get_option("gemm_x6") != 0 and K > 0 and K % 16 == 0 and M >= 1 and rows >= 4
-            and N >= 4 and 2.0 * rows * N * K >= 1.6e10)
+    return _lib.lib().grl_linear_fwd_path(int(M), int(K), int(N), int(path_rows)) != 0
 
 
-def _bwd_data_enabled() -> bool:
-    return _lib.get_option("graphconv_fused_bwd") != 0
+def _bwd_data_eligible(g: torch.Tensor, graph, W: torch.Tensor, F: int, width: int) -> bool:
+    """Whether the one-kernel data gradient may take g [num_rows, C], W
+    [segments * F, C] over `graph` with dX in column blocks at least `width`
+    wide: the graphconv_fused_bwd option, a graph that has a typed transpose,
+    operands of the layer's shapes, and the library's shape rule
+    (grl_graphconv_bwd_data_shape_ok) for the transpose's rows.  Cheap: asked
+    before the (cached, once per graph) transpose is built; the workspace
+    query on the transpose then decides."""
+    if (_lib.get_option("graphconv_fused_bwd") == 0 or isinstance(graph, EdgeBlockedGraph)
+            or not graph.transpose_ok):
+        return False
+    M, C = g.shape
+    if (graph.num_cols < graph.num_rows or graph.self_rows != graph.num_rows or M != graph.num_rows
+            or g.dtype != torch.float32 or not g.is_contiguous() or W.dtype != torch.float32
+            or tuple(W.shape) != (graph.segments * F, C)):
+        return False
+    # (a graph without columns -- an empty node-range shard -- launches nothing, so has no shape to refuse)
+    return graph.num_cols == 0 or _lib.lib().grl_graphconv_bwd_data_shape_ok(
+        graph.num_cols, graph.num_types, int(graph.has_self), C, width) != 0
 
 
 def graph_conv_bwd_data(g: torch.Tensor, graph: TypedGraph, W: torch.Tensor, F: int, relu_out=None,
@@ -309,19 +345,12 @@ def graph_conv_bwd_data(g: torch.Tensor, graph: TypedGraph, W: torch.Tensor, F: 
     option 0 disables it.  want_aggregate: return (dX, G_agg, g_eff) with G_agg =
     [A_drop,s^T g_eff]_s ([num_cols, segments * C], written by the same
     kernel) and g_eff the gradient through the ReLU, for dW_s = X^T G_agg_s."""
-    if not _bwd_data_enabled() or isinstance(graph, EdgeBlockedGraph) or not graph.transpose_ok:
-        return None
     M, C = g.shape
-    L, S = graph.num_types, graph.segments
+    S = graph.segments
     nblk = -(-F // FUSED_MAX_OUT)
     wblk = (-(-F // nblk) + 3) // 4 * 4 if nblk > 1 else F  # block width, a multiple of 4
     bounds = [(f0, min(F, f0 + wblk)) for f0 in range(0, F, wblk)]
-    # cheap pre-checks before the (cached, once per graph) transpose build; the library decides
-    if (C not in FUSED_WIDTHS or F % 4 or F > 2 * FUSED_MAX_OUT or L > 7 or graph.num_cols < graph.num_rows
-            or graph.self_rows != graph.num_rows or M != graph.num_rows
-            or 2.0 * graph.num_cols * S * C * min(b - a for a, b in bounds) < 1.6e10
-            or g.dtype != torch.float32 or not g.is_contiguous() or W.dtype != torch.float32
-            or tuple(W.shape) != (S * F, C)):
+    if nblk > 2 or not _bwd_data_eligible(g, graph, W, F, min(b - a for a, b in bounds)):  # (at most two blocks)
         return None
     gt, eid = graph.typed_transpose()
     gt = gt.with_dropedge(graph.dropedge)
@@ -332,8 +361,7 @@ def graph_conv_bwd_data(g: torch.Tensor, graph: TypedGraph, W: torch.Tensor, F: 
         return None
     if relu_out is not None:
         g = torch.where(relu_out > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device)
-    de = graph.dropedge.to_c() if graph.dropedge is not None else None
+    ws = _workspace(ws_bytes, g.device)
     stream = current_stream_handle(g.device)
     rows = graph.num_cols  # dX rows: every column of the graph (a shard's halo rows get partials)
     dX = torch.empty(rows, F, dtype=torch.float32, device=g.device)
@@ -343,8 +371,8 @@ def graph_conv_bwd_data(g: torch.Tensor, graph: TypedGraph, W: torch.Tensor, F: 
         Wb = W.contiguous() if len(bounds) == 1 else W.reshape(S, F, C)[:, f0:f1, :].reshape(S * w, C).contiguous()
         out = dX if len(bounds) == 1 else torch.empty(rows, w, dtype=torch.float32, device=g.device)
         call("grl_graphconv_bwd_data", ctypes.byref(csr), eid.data_ptr(), g.data_ptr(), g.stride(0), M, C,
-             Wb.data_ptr(), w, out.data_ptr(), G_agg.data_ptr() if G_agg is not None and i == 0 else None,
-             ctypes.byref(de) if de is not None else None, ws.data_ptr(), ws_bytes, stream)
+             Wb.data_ptr(), w, out.data_ptr(), _ptr(G_agg) if i == 0 else None, _de_ref(graph), ws.data_ptr(),
+             ws_bytes, stream)
         if len(bounds) > 1:
             dX[:, f0:f1] = out
     return (dX, G_agg, g) if want_aggregate else dX
@@ -372,14 +400,9 @@ def graph_conv_bwd_data_rows_views(g: torch.Tensor, graph: TypedGraph, W: torch.
     is outside the one-kernel path.  No device work beyond the cached
     transpose and split plans: a caller that must decide collectively
     (grl.dist rows_backward) asks this first, agrees, then launches."""
-    if not _bwd_data_enabled() or isinstance(graph, EdgeBlockedGraph) or not graph.transpose_ok:
+    if not _bwd_data_eligible(g, graph, W, F, F):
         return None
-    M, C = g.shape
-    L, S = graph.num_types, graph.segments
-    if (C not in FUSED_WIDTHS or F % 4 or F > FUSED_MAX_OUT or L > 7 or graph.num_cols < graph.num_rows
-            or graph.self_rows != graph.num_rows or M != graph.num_rows or g.dtype != torch.float32
-            or not g.is_contiguous() or W.dtype != torch.float32 or tuple(W.shape) != (S * F, C)):
-        return None
+    C = g.shape[1]
     for r0, r1 in blocks:
         if not (r0 == 0 or r0 >= graph.num_rows) or r1 < r0 or r1 > graph.num_cols:
             raise _lib.GrlError(f"row block [{r0}, {r1}) must start at 0 or at/after row {graph.num_rows}")
@@ -422,7 +445,6 @@ def graph_conv_bwd_data_rows(g: torch.Tensor, graph: TypedGraph, W: torch.Tensor
     gt, eid = graph.typed_transpose()
     Wc = W.contiguous()
     M, C = g.shape
-    de = graph.dropedge.to_c() if graph.dropedge is not None else None
     stream = current_stream_handle(g.device)
     ws = None
     for (r0, r1), view in zip(blocks, views):
@@ -432,8 +454,8 @@ def graph_conv_bwd_data_rows(g: torch.Tensor, graph: TypedGraph, W: torch.Tensor
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device)
             g_rows = M if r0 == 0 else 0  # the self term: forward rows only
             call("grl_graphconv_bwd_data", ctypes.byref(csr), eid.data_ptr(), g.data_ptr(), g.stride(0),
-                 min(g_rows, r1 - r0), C, Wc.data_ptr(), F, dX[r0:r1].data_ptr(), None,
-                 ctypes.byref(de) if de is not None else None, ws.data_ptr(), ws_bytes, stream)
+                 min(g_rows, r1 - r0), C, Wc.data_ptr(), F, dX[r0:r1].data_ptr(), None, _de_ref(graph),
+                 ws.data_ptr(), ws_bytes, stream)
         if on_block is not None:
             on_block(r0, r1)
     return True
@@ -509,33 +531,12 @@ def graph_conv_fwd_train(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=
     result is bitwise spmm_forward then linear_fwd.  out / Z: contiguous
     [num_rows, C] / [num_rows, segments * F] fp32 tensors to write (e.g. the
     row block of a streamed layer)."""
-    _require_device(X, "node features")
-    if X.dtype != torch.float32 or W.dtype != torch.float32:
-        raise _lib.GrlError("graph_conv_fwd_train: features and weights must be float32")
-    X2 = _rows_view(X)
-    if X2.shape[0] != graph.num_cols:
-        raise _lib.GrlError(f"features have {X2.shape[0]} rows, graph gathers from {graph.num_cols}")
-    F = X2.shape[1]
-    Wc = W.contiguous()
-    C = Wc.shape[1]
-    K = graph.segments * F
-    if Wc.shape[0] != K:
-        raise _lib.GrlError(f"weights have {Wc.shape[0]} rows, expected {graph.segments} x {F}")
-    bc = b.contiguous() if b is not None else None
-    for t, shape, what in ((out, (graph.num_rows, C), "out"), (Z, (graph.num_rows, K), "Z")):
-        if t is not None and (tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous()):
-            raise _lib.GrlError(f"graph_conv_fwd_train: {what} must be a contiguous float32 {shape} tensor")
-    if out is None:
-        out = torch.empty(graph.num_rows, C, dtype=torch.float32, device=X.device)
-    if Z is None:
-        Z = torch.empty(graph.num_rows, K, dtype=torch.float32, device=X.device)
-    csr = graph.csr_c(F)
+    X2, F, Wc, bc, out, Z = _forward_args("graph_conv_fwd_train", X, graph, W, b, out, Z, want_Z=True)
+    K, C = Wc.shape
     ws_bytes = _lib.lib().grl_linear_fwd_ex_workspace_size(graph.num_rows, K, C, graph.path_rows)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device) if ws_bytes else None
-    de = graph.dropedge.to_c() if graph.dropedge is not None else None
-    call("grl_graphconv_fwd_train", ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(),
-         bc.data_ptr() if bc is not None else None, C, int(relu), out.data_ptr(), Z.data_ptr(),
-         ctypes.byref(de) if de is not None else None, ws.data_ptr() if ws is not None else None, ws_bytes,
+    ws = _workspace(ws_bytes, X.device)
+    call("grl_graphconv_fwd_train", ctypes.byref(graph.csr_c(F)), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(),
+         _ptr(bc), C, int(relu), out.data_ptr(), Z.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes,
          current_stream_handle(X.device))
     return out, Z
 
@@ -548,34 +549,16 @@ def graph_conv_infer(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None
     and max_workspace_bytes bounds it (the call then works in row chunks,
     bitwise equal to the whole-graph result).  out: a contiguous
     [num_rows, C] float32 tensor to write (e.g. a row block of a halo table)."""
-    _require_device(X, "node features")
-    if X.dtype != torch.float32 or W.dtype != torch.float32:
-        raise _lib.GrlError("graph_conv_infer: features and weights must be float32")
-    X2 = _rows_view(X)
-    if X2.shape[0] != graph.num_cols:
-        raise _lib.GrlError(f"features have {X2.shape[0]} rows, graph gathers from {graph.num_cols}")
-    F = X2.shape[1]
-    Wc = W.contiguous()
+    X2, F, Wc, bc, out, _ = _forward_args("graph_conv_infer", X, graph, W, b, out)
     C = Wc.shape[1]
-    if Wc.shape[0] != graph.segments * F:
-        raise _lib.GrlError(f"weights have {Wc.shape[0]} rows, expected {graph.segments} x {F}")
-    bc = b.contiguous() if b is not None else None
-    if out is None:
-        out = torch.empty(graph.num_rows, C, dtype=torch.float32, device=X.device)
-    elif (tuple(out.shape) != (graph.num_rows, C) or out.dtype != torch.float32 or not out.is_contiguous()
-          or out.device != X.device):
-        raise _lib.GrlError(f"out must be a contiguous float32 ({graph.num_rows}, {C}) tensor on {X.device}")
     csr = graph.csr_c(F)
     # the fused one-kernel path needs only W's planes; else Z whole
     full = _lib.lib().grl_graphconv_fwd_workspace_query(ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F,
                                                          Wc.data_ptr(), C)
     ws_bytes = full if max_workspace_bytes is None else min(full, int(max_workspace_bytes))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device) if ws_bytes else None
-    de = graph.dropedge.to_c() if graph.dropedge is not None else None
-    call("grl_graphconv_fwd", ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(),
-         bc.data_ptr() if bc is not None else None, C, int(relu), out.data_ptr(),
-         ctypes.byref(de) if de is not None else None, ws.data_ptr() if ws is not None else None, ws_bytes,
-         current_stream_handle(X.device))
+    ws = _workspace(ws_bytes, X.device)
+    call("grl_graphconv_fwd", ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc), C,
+         int(relu), out.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes, current_stream_handle(X.device))
     return out
 
 
@@ -670,10 +653,9 @@ def linear_fwd_ex(X2: torch.Tensor, W: torch.Tensor, w_layout: int, b, relu: boo
     if out is None:
         out = torch.empty(M, C, dtype=torch.float32, device=X2.device)
     ws_bytes = _lib.lib().grl_linear_fwd_ex_workspace_size(M, K, C, int(path_rows))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X2.device) if ws_bytes else None
-    call("grl_linear_fwd_ex", X2.data_ptr(), X2.stride(0), W.data_ptr(), int(w_layout),
-         b.data_ptr() if b is not None else None, out.data_ptr(), M, K, C, int(relu), int(path_rows),
-         ws.data_ptr() if ws is not None else None, ws_bytes, current_stream_handle(X2.device))
+    ws = _workspace(ws_bytes, X2.device)
+    call("grl_linear_fwd_ex", X2.data_ptr(), X2.stride(0), W.data_ptr(), int(w_layout), _ptr(b), out.data_ptr(), M, K,
+         C, int(relu), int(path_rows), _ptr(ws), ws_bytes, current_stream_handle(X2.device))
     return out
 
 
@@ -799,10 +781,9 @@ def node_attention_forward(Q, K, H, V, gamma, stats: bool = False, q_range=None)
     onorm = alloc(V) if stats else None
     rmax = alloc(V[..., 0]) if stats else None
     rsum = (torch.ones_like(V[..., 0]) if q_range is not None else torch.empty_like(V[..., 0])) if stats else None
-    ptr = (lambda t: t.data_ptr() if t is not None else None)  # noqa: E731
     ws, ws_bytes = _attn_workspace(B, N, dk, dv, V.device)
     call("grl_node_attention_fwd_rows", Q.data_ptr(), K.data_ptr(), H.data_ptr(), V.data_ptr(), gamma.data_ptr(),
-         out.data_ptr(), ptr(onorm), ptr(rmax), ptr(rsum), B, N, dk, dv, q0, q1, ptr(ws), ws_bytes,
+         out.data_ptr(), _ptr(onorm), _ptr(rmax), _ptr(rsum), B, N, dk, dv, q0, q1, _ptr(ws), ws_bytes,
          current_stream_handle(V.device))
     return (out, onorm, rmax, rsum) if stats else out
 
@@ -829,7 +810,7 @@ def node_attention_backward(Q, K, H, gamma, onorm, rmax, rsum, dout, q_range=Non
         ws, ws_bytes = _attn_workspace(B, N, dk, b - a, Q.device, backward=True)
         call("grl_node_attention_bwd_rows", Q.data_ptr(), K.data_ptr(), H_b.data_ptr(), dO_b.data_ptr(),
              rmax.data_ptr(), rsum.data_ptr(), D.data_ptr(), dQ_b.data_ptr(), dK_b.data_ptr(), dH_b.data_ptr(),
-             B, N, dk, b - a, q0, q1, ws.data_ptr() if ws is not None else None, ws_bytes,
+             B, N, dk, b - a, q0, q1, _ptr(ws), ws_bytes,
              current_stream_handle(Q.device))
         dQ = dQ_b if dQ is None else dQ + dQ_b
         dK = dK_b if dK is None else dK + dK_b
@@ -867,8 +848,8 @@ def bag_linear_forward(V2: torch.Tensor, Wt: torch.Tensor, b, relu: bool) -> tor
     M, K = V2.shape
     C = Wt.shape[1]
     out = torch.empty(M, C, dtype=torch.float32, device=V2.device)
-    call("grl_bag_linear_fwd", V2.data_ptr(), V2.stride(0), M, K, Wt.data_ptr(), C,
-         b.data_ptr() if b is not None else None, int(relu), out.data_ptr(), current_stream_handle(V2.device))
+    call("grl_bag_linear_fwd", V2.data_ptr(), V2.stride(0), M, K, Wt.data_ptr(), C, _ptr(b), int(relu),
+         out.data_ptr(), current_stream_handle(V2.device))
     return out
 
 
@@ -887,10 +868,8 @@ def bag_linear_bwd_weight(V2: torch.Tensor, g: torch.Tensor, relu_out, want_db: 
     db = torch.empty(C, dtype=torch.float32, device=g.device) if want_db else None
     ws_bytes = _lib.lib().grl_bag_linear_bwd_weight_workspace_size(M, K, C)
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=g.device)
-    call("grl_bag_linear_bwd_weight", V2.data_ptr(), V2.stride(0), g.data_ptr(),
-         relu_out.data_ptr() if relu_out is not None else None, dWt.data_ptr(),
-         db.data_ptr() if db is not None else None, M, K, C, ws.data_ptr(), ws_bytes,
-         current_stream_handle(g.device))
+    call("grl_bag_linear_bwd_weight", V2.data_ptr(), V2.stride(0), g.data_ptr(), _ptr(relu_out), dWt.data_ptr(),
+         _ptr(db), M, K, C, ws.data_ptr(), ws_bytes, current_stream_handle(g.device))
     return dWt, db
 
 

@@ -331,6 +331,18 @@ int grl_linear_fwd_ex(const float* Z, int64_t ldz, const float* W,
                       int64_t path_rows, void* workspace,
                       size_t workspace_bytes, grl_stream_t stream);
 
+/* The GEMM path of grl_linear_fwd_ex(M, K, C, path_rows) under the current
+ * path options: 1 = the x6 GEMM, 0 = an fp32-MFMA form.  1 exactly when
+ * M >= 1, K % 16 == 0, C >= 4, gemm_x6 is on and, for R = max(M, path_rows)
+ * rows, R >= 4 and 2 R C K >= 1.6e10 flops -- the calls for which
+ * grl_linear_fwd_ex_workspace_size() is the size of W's planes,
+ * 3 * roundup(C, 256) * K * 2 + 256 bytes.  A host layer that cuts a layer
+ * into row blocks (grl/dist.py) asks this, with the whole layer's rows as
+ * path_rows, to keep every block on the whole call's path.  Host-only, no
+ * device work.                                                             */
+int32_t grl_linear_fwd_path(int64_t M, int32_t K, int32_t C,
+                            int64_t path_rows);
+
 /* One GraphConv layer forward in one call (inference):
  *   out = relu?( (A_drop X) W + bias )       robust_gcn.py:45-51 (+ the F.relu
  * of drop_robust_gcn.py:76), i.e. grl_typed_spmm_fwd then grl_linear_fwd with
@@ -410,6 +422,20 @@ int grl_graphconv_bwd_data(const GrlTypedCsr* gt, const int32_t* eid,
                            float* G_agg, const GrlDropEdge* de,
                            void* workspace, size_t workspace_bytes,
                            grl_stream_t stream);
+
+/* The shape half of grl_graphconv_bwd_data's eligibility, for a host layer
+ * that decides before it builds the typed transpose: 1 when graphconv_fused
+ * is on, C is 64, 128, 256, 512 or 1024, 1 <= F <= 512 with F % 4 == 0,
+ * 1 <= num_types <= 7, and the [rows, S C] x [S C, F] product (S = has_self +
+ * num_types, rows = the transpose's rows) takes the x6 GEMM
+ * (grl_linear_fwd_path(rows, S C, F, 0)); else 0.  The workspace query is
+ * nonzero exactly when this holds for gt's rows and the call's pointers and
+ * plan qualify too: gt->self_row0 == 0, G and W 16-B aligned, ldg % 4 == 0,
+ * ldg < 2^30, no heavy-row split plan, nnz < 2^31.  Host-only, no device
+ * work.                                                                     */
+int32_t grl_graphconv_bwd_data_shape_ok(int64_t rows, int32_t num_types,
+                                        int32_t has_self, int32_t C,
+                                        int32_t F);
 
 /* Backward of grl_linear_fwd (autograd MmBackward0 of robust_gcn.py:50, with
  * the ReLU of drop_robust_gcn.py:76 folded in when relu_out != NULL):

@@ -98,3 +98,45 @@ def test_path_options_round_trip_and_reject_unknown_names():
         assert x6_rows_ok(1_000_000, 256, 1792)
     finally:
         del os.environ["GRL_GEMM_X6"]
+
+
+# (M, K, C, path_rows) -> grl_linear_fwd_path, from the rule in grl.h: gemm_x6 on, M >= 1, K % 16 == 0, C >= 4,
+# R = max(M, path_rows) >= 4 and 2 R C K >= 1.6e10 (2 * 17439 * 256 * 1792 = 16_000_143_360 >= 1.6e10 >
+# 15_999_225_856 = 2 * 17438 * 256 * 1792)
+LINEAR_PATH_CASES = [((17438, 1792, 256, 0), 0), ((17439, 1792, 256, 0), 1), ((1, 1792, 256, 1_000_000), 1),
+                     ((0, 1792, 256, 1_000_000), 0), ((1_000_000, 1800, 256, 0), 0), ((1_000_000_000, 1792, 3, 0), 0)]
+
+
+def test_linear_fwd_path_is_the_x6_rule_and_x6_rows_ok_asks_it():
+    import grl
+    from grl.ops import x6_rows_ok
+
+    lib = _lib.lib()
+    for (M, K, C, pr), want in LINEAR_PATH_CASES:
+        assert lib.grl_linear_fwd_path(M, K, C, pr) == want, (M, K, C, pr)
+        assert x6_rows_ok(M, C, K, pr) is bool(want), (M, K, C, pr)
+        if want:  # the x6 path's workspace: W's three bf16 planes, C rounded up to the 256-column tile
+            assert lib.grl_linear_fwd_ex_workspace_size(M, K, C, pr) == 3 * (-(-C // 256) * 256) * K * 2 + 256
+        with grl.options(gemm_x6=0):
+            assert lib.grl_linear_fwd_path(M, K, C, pr) == 0 and not x6_rows_ok(M, C, K, pr), (M, K, C, pr)
+
+
+# (rows, L, has_self, C, F) -> grl_graphconv_bwd_data_shape_ok, from the rule in grl.h: C in {64, 128, 256, 512,
+# 1024}, 1 <= F <= 512, F % 4 == 0, L <= 7, and the x6 floor on [rows, S C] x [S C, F]
+BWD_DATA_SHAPE_CASES = [((1_000_000, 6, 1, 256, 256), 1), ((1_000_000, 6, 1, 512, 512), 1),
+                        ((1_000_000, 6, 1, 256, 516), 0), ((1_000_000, 6, 1, 200, 256), 0),
+                        ((1_000_000, 6, 1, 256, 254), 0), ((1_000_000, 8, 1, 256, 256), 0),
+                        ((1000, 6, 1, 256, 256), 0)]
+
+
+def test_graphconv_bwd_data_shape_ok_is_the_documented_rule():
+    import grl
+    from grl import ops
+
+    lib = _lib.lib()
+    for args, want in BWD_DATA_SHAPE_CASES:
+        assert lib.grl_graphconv_bwd_data_shape_ok(*args) == want, args
+        with grl.options(graphconv_fused=0):
+            assert lib.grl_graphconv_bwd_data_shape_ok(*args) == 0, args
+    # F = 512 passes and F = 516 (a multiple of 4) does not: the column blocks ops cuts are the library's widest
+    assert ops.FUSED_MAX_OUT == 512

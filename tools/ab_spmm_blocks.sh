@@ -1,4 +1,4 @@
-# A/B of the persistent SpMM grid size (GRL_SPMM_BLOCKS_PER_CU, four-wave
+# A/B of the persistent SpMM grid size (the spmm_blocks_per_cu path option, four-wave
 # blocks per CU; read per process): C3 forward p=0 (the headline kernel),
 # forward p=0.3 and the CSC backward p=0.3, from bench.py's own line.
 # Usage: bash tools/ab_spmm_blocks.sh "16 24" [rounds]

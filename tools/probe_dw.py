@@ -1,17 +1,22 @@
 """Probe: the x6 weight-gradient GEMM at C3 (dW = Z^T g: M = 1M nodes, K =
 1792, C = 256; grl_linear_bwd_weight), HIP events over back-to-back calls,
-with the library GRL_LIB_PATH names; checks the result against the default
-library's bits when AB_REF is set."""
+with the library GRL_LIB_PATH names and the NAME=VALUE path options given as
+arguments (grl.set_option); with AB_SAVE set, saves dW or, when the file
+exists, checks the result's bits against it."""
 import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "graph-representation-learning_amd"))
 import torch  # noqa: E402
 
+from grl import set_option  # noqa: E402
 from grl.ops import linear_bwd_weight  # noqa: E402
 
 
 def main():
+    opts = sys.argv[1:]
+    for kv in opts:
+        set_option(kv.split("=")[0], int(kv.split("=")[1]))
     dev = torch.device("cuda:0")
     gen = torch.Generator(device=dev).manual_seed(3)
     M, K, C = 1_000_000, 1792, 256
@@ -35,7 +40,7 @@ def main():
             same = bool(torch.equal(ref, dW.cpu()))
         else:
             torch.save(dW.cpu(), out)
-    print(f"{lib}: dW {ms:.3f} ms ({2.0 * M * K * C / ms / 1e9:.1f} TF fp32-eq) bitwise_vs_first={same}", flush=True)
+    print(f"{lib} {' '.join(opts)}: dW {ms:.3f} ms ({2.0 * M * K * C / ms / 1e9:.1f} TF fp32-eq) bitwise_vs_first={same}", flush=True)
 
 
 if __name__ == "__main__":

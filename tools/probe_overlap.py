@@ -8,7 +8,7 @@ import sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "graph-representation-learning_amd"))
 import torch  # noqa: E402
 
-from grl import TypedGraph  # noqa: E402
+from grl import TypedGraph, get_option  # noqa: E402
 from grl.ops import linear_fwd, spmm_forward  # noqa: E402
 
 
@@ -60,6 +60,6 @@ def both_gemm_first():
 
 
 a, c = timeit(spmm), timeit(gemm)
-print(f"blocks/CU={os.environ.get('GRL_SPMM_BLOCKS_PER_CU', '16')}: spmm {a:.3f} ms, gemm {c:.3f} ms, "
+print(f"blocks/CU={get_option('spmm_blocks_per_cu')}: spmm {a:.3f} ms, gemm {c:.3f} ms, "
       f"sum {a + c:.3f}, concurrent {timeit(both):.3f} ms, gemm launched first {timeit(both_gemm_first):.3f} ms",
       flush=True)

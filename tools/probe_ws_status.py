@@ -1,14 +1,15 @@
 """A/B probe: the persistent one-kernel GraphConv (graphconv_ws_kernel) at C3
 (N=1M, avg_deg 32, L=6, F=C=256): inference p=0 / p=0.3 and the data
 gradient p=0.3, HIP events over back-to-back calls; the library under test is
-GRL_LIB_PATH (default the in-tree libgrl.so), GRL_WS_STATUS as set."""
+GRL_LIB_PATH (default the in-tree libgrl.so); the tag records the
+ws_status_sync path option."""
 import os
 import sys
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "graph-representation-learning_amd"))
 import torch  # noqa: E402
 
-from grl import DropEdge, TypedGraph  # noqa: E402
+from grl import DropEdge, TypedGraph, get_option  # noqa: E402
 from grl.ops import graph_conv_bwd_data, graph_conv_infer  # noqa: E402
 
 
@@ -37,7 +38,7 @@ def main():
     gd = g0.with_dropedge(DropEdge(0.3, 2, 1, True))
     gd.typed_transpose()
     lib = os.path.basename(os.environ.get("GRL_LIB_PATH", "libgrl.so"))
-    tag = f"{lib} status={os.environ.get('GRL_WS_STATUS', 'sync')}"
+    tag = f"{lib} ws_status_sync={get_option('ws_status_sync')}"
     r = [timeit(lambda: graph_conv_infer(X, g0, W, b, True)), timeit(lambda: graph_conv_infer(X, gd, W, b, True)),
          timeit(lambda: graph_conv_bwd_data(G, gd, W, F))]
     same = None

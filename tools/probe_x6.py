@@ -1,6 +1,6 @@
 """Diagnostic: split-bf16 ("x6") vs fp32-MFMA GEMMs at the C3 layer shape.
-Runs itself twice (path option gemm_x6 = 1 / 0, one child process each)
-and prints time, TFLOP/s and the error vs fp64 on sampled rows, relative to
+Runs itself twice (path option gemm_x6 = 1 / 0, one child process each:
+`probe_x6.py child VALUE` is one such run) and prints time, TFLOP/s and the error vs fp64 on sampled rows, relative to
 sum |terms| per element (the test suite's criterion)."""
 import json
 import os
@@ -12,7 +12,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 def child():
     import torch
-    from grl import set_option
+    from grl import get_option, set_option
     from grl.ops import linear_bwd_data, linear_fwd
 
     set_option("gemm_x6", int(sys.argv[2]))
@@ -36,7 +36,7 @@ def child():
     b = torch.randn(C, device=dev, generator=gen)
     g = torch.randn(M, C, device=dev, generator=gen)
     fl = 2.0 * M * K * C / 1e12
-    res = {"x6": os.environ.get("GRL_GEMM_X6", "1")}
+    res = {"x6": get_option("gemm_x6")}
     rows = torch.randint(0, M, (4096,), device=dev, generator=gen)
     out = linear_fwd(Z, W, b, False)
     ref = Z[rows].double() @ W.double() + b.double()
