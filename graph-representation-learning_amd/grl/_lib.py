@@ -139,6 +139,8 @@ SIGNATURES = {
     "grl_typed_spmm_fwd": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_fwd_slice": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_i64, _c_vp, _c_i64, _c_i32,
                                           _P(GrlDropEdge), _c_vp]),
+    "grl_typed_spmm_fwd_bf16": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_i64, _c_vp, _c_i64, _c_i32,
+                                         _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_bwd": (_c_i32, [_P(GrlTypedCsc), _c_vp, _c_i32, _c_vp, _c_i64, _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_bwd_accum": (_c_i32, [_P(GrlTypedCsc), _c_vp, _c_i32, _c_vp, _c_i64, _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_bwd_slice": (_c_i32, [_P(GrlTypedCsc), _c_vp, _c_i32, _c_i32, _c_i32, _c_vp, _c_i64,

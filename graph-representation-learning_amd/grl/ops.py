@@ -44,15 +44,21 @@ def _de_ref(graph):
     return ctypes.byref(graph.dropedge.to_c()) if graph.dropedge is not None else None
 
 
+# What the aggregation gathers from: fp32, or bf16 read as stored and widened
+# on the fly (grl_typed_spmm_fwd_bf16) -- never through a widened copy.
+_TABLE_DTYPES = (torch.float32, torch.bfloat16)
+
+
 def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: bool = False):
     """The checked operands of a forward over `graph` -- (X2, F, Wc, bc, out,
     Z): the features' 2-D row view and width, the contiguous weights
     [segments * F, C] and bias (None without), out [num_rows, C] (with
     weights) and Z [num_rows, segments * F] (want_Z), each the contiguous
-    fp32 tensor given or a new one."""
+    fp32 tensor given or a new one.  Without weights (the aggregation alone)
+    the features may be bfloat16."""
     _require_device(X, "node features")
-    if W is None and X.dtype != torch.float32:
-        raise _lib.GrlError(f"node features must be float32 (got {X.dtype})")
+    if W is None and X.dtype not in _TABLE_DTYPES:
+        raise _lib.GrlError(f"node features must be float32 or bfloat16 (got {X.dtype})")
     if W is not None and (X.dtype != torch.float32 or W.dtype != torch.float32):
         raise _lib.GrlError(f"{who}: features and weights must be float32")
     X2 = _rows_view(X)
@@ -78,10 +84,16 @@ def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: 
 
 def spmm_forward(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor = None) -> torch.Tensor:
     """Z = A_drop X without autograd bookkeeping, optionally into `out`
-    (contiguous [num_rows, segments*F] fp32): the inference / benchmark form."""
+    (contiguous [num_rows, segments*F] fp32): the inference / benchmark form.
+    X float32 or bfloat16 (read as stored: half the gather bytes, Z bitwise
+    the fp32 result on X.float())."""
     if isinstance(graph, EdgeBlockedGraph):
         return _blocked_forward(X, graph, out)
     X2, F, _, _, _, Z = _forward_args("spmm_forward", X, graph, Z=out, want_Z=True)
+    if X2.dtype == torch.bfloat16:
+        call("grl_typed_spmm_fwd_bf16", ctypes.byref(graph.csr_c(F)), X2.data_ptr(), X2.stride(0), F, 0, Z.data_ptr(),
+             graph.segments * F, F, _de_ref(graph), current_stream_handle(X.device))
+        return Z
     call("grl_typed_spmm_fwd", ctypes.byref(graph.csr_c(F)), X2.data_ptr(), X2.stride(0), F, Z.data_ptr(),
          _de_ref(graph), current_stream_handle(X.device))
     return Z
@@ -92,12 +104,13 @@ def spmm_forward_slice(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor, co
     """Columns [col0, col0 + F) of Z = A_drop X into `out` (contiguous
     [num_rows, segments * F_total]), where X is that column slice's table
     ([graph.num_cols, F], any row stride) and row n's self term reads X row
-    self_col0 + n (grl_typed_spmm_fwd_slice).  Bitwise equal, per element,
-    to the whole-width spmm_forward: the pipelined halo exchange of grl.dist
-    aggregates one slice while the next is in flight."""
+    self_col0 + n (grl_typed_spmm_fwd_slice; a bfloat16 table:
+    grl_typed_spmm_fwd_bf16).  Bitwise equal, per element, to the whole-width
+    spmm_forward: the pipelined halo exchange of grl.dist aggregates one slice
+    while the next is in flight."""
     _require_device(X, "node features")
-    if X.dtype != torch.float32 or X.dim() != 2 or X.stride(1) != 1:
-        raise _lib.GrlError("slice table must be a 2-D float32 tensor with unit column stride")
+    if X.dtype not in _TABLE_DTYPES or X.dim() != 2 or X.stride(1) != 1:
+        raise _lib.GrlError("slice table must be a 2-D float32 or bfloat16 tensor with unit column stride")
     if X.shape[0] != graph.num_cols:
         raise _lib.GrlError(f"slice table has {X.shape[0]} rows, graph gathers from {graph.num_cols}")
     F = X.shape[1]
@@ -108,7 +121,8 @@ def spmm_forward_slice(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor, co
     zseg = out.shape[1] // S
     if col0 < 0 or col0 + F > zseg:
         raise _lib.GrlError(f"columns [{col0}, {col0 + F}) outside the {zseg}-column segments")
-    call("grl_typed_spmm_fwd_slice", ctypes.byref(graph.csr_c(F)), X.data_ptr(), X.stride(0), F, int(self_col0),
+    entry = "grl_typed_spmm_fwd_bf16" if X.dtype == torch.bfloat16 else "grl_typed_spmm_fwd_slice"
+    call(entry, ctypes.byref(graph.csr_c(F)), X.data_ptr(), X.stride(0), F, int(self_col0),
          out.data_ptr() + 4 * col0, out.stride(0), zseg, _de_ref(graph), current_stream_handle(X.device))
     return out
 
@@ -186,16 +200,21 @@ class _TypedAggregate(torch.autograd.Function):
         Z = spmm_forward(X, graph)
         ctx.graph = graph
         ctx.xshape = X.shape
+        ctx.xdtype = X.dtype
         return Z
 
     @staticmethod
     def backward(ctx, dZ: torch.Tensor):
-        return spmm_backward(dZ, ctx.graph, ctx.xshape[-1]).view(ctx.xshape), None
+        # Z is fp32 whatever X is, so dZ is: one fp32 transpose pass, rounded once for a bf16 X
+        return spmm_backward(dZ, ctx.graph, ctx.xshape[-1]).view(ctx.xshape).to(ctx.xdtype), None
 
 
 def typed_aggregate(X: torch.Tensor, graph: TypedGraph) -> torch.Tensor:
     """Z[n, s*F:(s+1)*F]: segment 0 = own row (identity block), segment 1+t =
-    sum over type-t neighbours; rows of X = graph.num_cols."""
+    sum over type-t neighbours; rows of X = graph.num_cols.  X float32 or
+    bfloat16 (unit column stride, any row stride; a column-slice view is read
+    in place); Z is fp32 either way, and a bfloat16 X gets a bfloat16
+    gradient: the fp32 dX rounded to nearest even."""
     return _TypedAggregate.apply(X, graph)
 
 
@@ -585,7 +604,15 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
     re-aggregated (one more SpMM pass) and every gradient is bitwise the
     saved-Z path's.  Peak memory in the G_s form: the transient G_agg
     [num_cols, (L+1) C] of the backward is Z-sized when C == F, so recompute
-    lowers the memory held BETWEEN the passes, not the backward's peak."""
+    lowers the memory held BETWEEN the passes, not the backward's peak.
+    A bfloat16 X (fp32 W, b) runs typed_aggregate then graph_linear, two
+    autograd nodes: the one-kernel GraphConv kernels take fp32 features only.
+    out is bitwise the layer's on X.float(), dW and db those of its saved-Z
+    path, X.grad that path's dX rounded to bfloat16."""
+    if X.dtype == torch.bfloat16:
+        if W.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
+            raise _lib.GrlError("graph_conv: weights and bias must be float32")
+        return graph_linear(typed_aggregate(X, graph), W, b, relu, getattr(graph, "path_rows", 0))
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (X, W, b))):
         if isinstance(graph, EdgeBlockedGraph):  # one int32 CSR per call: aggregate by blocks, then the linear
             return linear_fwd(spmm_forward(X, graph), W.contiguous(), b.contiguous() if b is not None else None,

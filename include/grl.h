@@ -257,6 +257,22 @@ int grl_typed_spmm_fwd_slice(const GrlTypedCsr* g, const float* X, int64_t ldx,
                              int64_t ldz, int32_t zseg, const GrlDropEdge* de,
                              grl_stream_t stream);
 
+/* Z = A_drop X with X stored as bf16 bits (the upper 16 bits of the fp32
+ * value, as torch.bfloat16 keeps them); ldx counted in bf16 elements.  The
+ * arguments and the layout of Z are grl_typed_spmm_fwd_slice's; whole graph:
+ * self_col0 = 0, ldz = segments*F, zseg = F.  Z stays fp32: every gathered
+ * element is widened exactly (bits << 16) and accumulated by the same fmaf
+ * chain in CSR order, so Z is bitwise what grl_typed_spmm_fwd[_slice] gives
+ * on the widened table, at half the gather bytes and half the table memory.
+ * 16 B loads (8 columns a lane) when X is 16 B-aligned, ldx % 8 == 0 and
+ * F % 8 == 0 and Z takes float4 stores; one element a lane otherwise.
+ * Mixed-precision training keeps node features in bf16; the gradient of
+ * this call is grl_typed_spmm_bwd on the fp32 dZ, rounded by the caller.   */
+int grl_typed_spmm_fwd_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx,
+                            int32_t F, int64_t self_col0, float* Z,
+                            int64_t ldz, int32_t zseg, const GrlDropEdge* de,
+                            grl_stream_t stream);
+
 /* dX = A_drop^T dZ.  Replaces autograd's BmmBackward0 for robust_gcn.py:45
  * (grad of V through the aggregation), with the same DropEdge mask as the
  * forward call that used `de`.  dZ: contiguous [*, (has_self+num_types)*F];
