@@ -11,7 +11,11 @@
 //    waves and MFMA waves specialised and coupled by an LDS ring of Z tiles
 //    (64 rows x 128 columns); see its comment below;
 //  * graphconv_fused_kernel (fg_ws = 0): 32-row tiles, every wave
-//    alternates gather and multiply phases, three workgroups per CU.
+//    alternates gather and multiply phases, three workgroups per CU;
+//  * graphconv_ws_bf16_kernel: graphconv_ws_kernel over a table of bf16 bits
+//    (grl_graphconv_fwd_bf16, _fwd_train_bf16): the same body text
+//    (graphconv_ws_body.inc) with 8 B-per-lane gather loads widened at the
+//    fmaf, bitwise the fp32 kernel on the widened table.
 // Shared pieces: the gather sums a wave's rows' segment-t neighbour rows
 // (one float4 per lane, one 1 KB row per wave-instruction, the rows' edge
 // lists streamed as one list with flushes at row boundaries); the multiply
@@ -34,6 +38,7 @@
 
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 // Diagnostic switches (GRL_WS_STAMP, GRL_WS_ONLY_ROLE, GRL_WS_DIAG_*,
@@ -419,6 +424,13 @@ constexpr int WS_NB = (140 * 1024) / (WS_SLOT * 4);  // ring slots that ~140 KB 
 #ifndef GRL_WS_U16
 #define GRL_WS_U16 12
 #endif
+// the bf16-table kernel's rows in flight (2 dwords a row, not 4): its own knobs
+#ifndef GRL_WS_BF16_U
+#define GRL_WS_BF16_U 12
+#endif
+#ifndef GRL_WS_BF16_U16
+#define GRL_WS_BF16_U16 12
+#endif
 constexpr int WS_SPIN = 1 << 24;           // bounded waits (~0.5 s of s_sleep 1); the ws_spin path option overrides
 constexpr int WS_STATUS_TIMEOUT = 1;       // status bit: a bounded wait ran out (results invalid)
 
@@ -478,6 +490,14 @@ __device__ __forceinline__ bool wait_ge(int* p, int target, unsigned long long* 
 #ifndef GRL_WS_DIAG_LB
 #define GRL_WS_DIAG_LB (64 * WS_WAVES)  // register-use diagnostics: a smaller bound shows the unconstrained demand
 #endif
+// The kernel's body is graphconv_ws_body.inc, shared as text by the fp32
+// kernel and the bf16-table kernel below it (why, and what differs: there).
+
+// a lane's 4 bf16 columns as loaded -> fp32, exactly
+__device__ __forceinline__ float4 widen4(const uint2& b) {
+  return make_float4(lo_f(b.x), hi_f(b.x), lo_f(b.y), hi_f(b.y));
+}
+
 template <int KS, bool VALS, bool EID = false, int FV = 1, int PROD = 8>
 __global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_kernel(
     int64_t M, int L, int hs, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
@@ -486,417 +506,27 @@ __global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_kernel(
     float* __restrict__ out, int C, DropDev de, int64_t num_tiles, float* __restrict__ Zout, int64_t ldz,
     const int32_t* __restrict__ eid, int64_t self_rows, int spin_limit, int* __restrict__ status,
     int64_t self_row0) {
-  constexpr int FVW = KS * 16;                // columns per virtual segment
-  constexpr int F = FVW * FV;                 // columns per segment
-  constexpr int KC = FVW < WS_KC ? FVW : WS_KC;  // Z columns per unit
-  constexpr int NH = FVW / KC;                // units per virtual segment
-  constexpr int KSU = KC / 16;                // K16 steps per unit
-  constexpr int CONS = WS_WAVES - PROD;       // MFMA waves
-  constexpr int CB = CONS * WS_CB;            // 32-column blocks of W's planes (C <= 32 CB)
-  constexpr int RW = WS_R / PROD;             // rows per gather wave
-  constexpr int U = RW > 8 ? GRL_WS_U16 : GRL_WS_U;  // neighbour rows in flight per gather wave
-  static_assert(FV == 1 || FVW == WS_FV, "wide segments are cut into 256-column virtual segments");
-  static_assert(NH < WS_NB, "a virtual segment's units are distinct ring slots, and one more is free");
-  static_assert(PROD == 8 || PROD == 4, "8 gather + 4 MFMA waves, or 4 + 8 (two 8-row groups per gather wave)");
-  __shared__ __attribute__((aligned(16))) float ring[WS_NB * WS_SLOT];
-  __shared__ int produced[WS_NB], consumed[WS_NB];
-  if (threadIdx.x < WS_NB) {
-    produced[threadIdx.x] = 0;
-    consumed[threadIdx.x] = 0;
-  }
-  __syncthreads();
-  de = resolve_key(de);
-  const int lane = threadIdx.x & 63;
-  const int wave = uniform_i(threadIdx.x >> 6);
-  const int S = L + hs;
-  unsigned long long waited = 0;
-#if GRL_WS_STAMP
-  const unsigned long long t_start = __builtin_amdgcn_s_memtime();
-  auto stamp_out = [&]() {
-    if (lane == 0 && blockIdx.x < 1024) {
-      g_ws_dbg[(blockIdx.x * 12 + wave) * 2] = waited;
-      g_ws_dbg[(blockIdx.x * 12 + wave) * 2 + 1] = __builtin_amdgcn_s_memtime() - t_start;
-    }
-  };
-#else
-  auto stamp_out = [&]() {};
-#endif
+#define GRL_WS_BF16 0
+#include "graphconv_ws_body.inc"
+#undef GRL_WS_BF16
+}
 
-#if GRL_WS_ONLY_ROLE == 2
-  if (false) {
-#else
-  if (wave < PROD) {
-#endif
-    // =========================== gather waves ===========================
-    // A gather wave's RW rows are NG groups of GR = 8; each group's edges of a
-    // segment stream as one list (the rowptr window of 8 rows fits one
-    // register), the groups one after the other.
-    constexpr int GR = 8;
-    constexpr int NG = RW / GR;
-#ifndef GRL_WS_SC
-#define GRL_WS_SC 4
-#endif
-    constexpr int SC = GRL_WS_SC;        // self rows loaded per step
-    const int col = lane * 4;            // this lane's 4 columns of the virtual segment
-    const bool col_ok = col < FVW;
-    const int part = col / KC;           // the unit (part of the virtual segment) they belong to
-    const int ucol = col - part * KC;    // column within that unit
-    int u = 0;                           // first unit of the current virtual segment
-    // segment lists: lanes < GR hold row lane's range start b and the
-    // inclusive count incl; the first 64 entries' source rows / weights are
-    // fetched one list ahead
-    struct List {
-      int b, incl, exc, total, sidx;
-      float w;
-    };
-    auto make_list = [&](int rp, int t) {
-      List ls;
-      const int r = min(lane, GR - 1);
-      ls.b = __shfl(rp, r * L + t);
-      const int e1 = __shfl(rp, r * L + t + 1);  // all lanes: ds_bpermute reads active lanes only
-      const int cnt = lane < GR ? e1 - ls.b : 0;
-      int incl = cnt;
-#pragma unroll
-      for (int d = 1; d < GR; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (lane >= d) incl += v;
-      }
-      ls.incl = incl;
-      ls.exc = incl - cnt;
-      ls.total = readlane_i(incl, GR - 1);
-      return ls;
-    };
-    // list entries [c0, c0 + 64): source row and DropEdge weight (0 = dropped / past the end)
-    auto fetch = [&](const List& ls, int c0, int& sidx, float& w) {
-      const int pp = c0 + lane;
-      int sl = 0;
-#pragma unroll
-      for (int i = 0; i < GR - 1; ++i) sl += pp >= readlane_i(ls.incl, i) ? 1 : 0;
-      const int e = __shfl(ls.b, sl) + (pp - __shfl(ls.exc, sl));  // CSR position of entry pp
-      sidx = 0;
-      w = 0.0f;
-      if (pp < ls.total) {
-        sidx = colidx[e];
-        const float v = VALS ? vals[e] : 1.0f;
-        if (EID)
-          w = de.active ? dropedge_weight(de, v, edge_base + (uint64_t)(uint32_t)eid[e]) : v;
-        else
-          w = de.active ? dropedge_weight(de, v, edge_base + (uint64_t)e) : v;
-      }
-    };
-    for (int64_t tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) {
-      const int64_t rw0 = tile * WS_R + wave * RW;
-      const int nvalid = (int)max<int64_t>(0, min<int64_t>(RW, M - rw0));
-      // rowptr window of each group's rows (lane l: rowptr[(rw0 + 8 g) L + l], l <= 8 L; rows past M read as empty)
-      int rp[NG];
-#pragma unroll
-      for (int gi = 0; gi < NG; ++gi) {
-        const int nv = max(0, min(GR, nvalid - gi * GR));
-        rp[gi] = lane <= GR * L ? rowptr[min<int64_t>((rw0 + gi * GR) * L + min(lane, nv * L), M * L)] : 0;
-      }
-      List cur = make_list(rp[0], 0);
-      fetch(cur, 0, cur.sidx, cur.w);
-      for (int s = 0; s < S; ++s) {
-#pragma unroll 1
-        for (int hv = 0; hv < FV; ++hv, u += NH) {
-          // claim the virtual segment's NH slots (this wave's rows only), once, before the first store
-          bool have = false;
-          auto claim = [&]() -> bool {
-            if (have) return true;
-#pragma unroll
-            for (int q = 0; q < NH; ++q)
-              if (!wait_ge(&consumed[(u + q) % WS_NB], CONS * ((u + q) / WS_NB), &waited, spin_limit, status))
-                return false;
-            have = true;
-            return true;
-          };
-          float* const dst = ring + ((u + part) % WS_NB) * WS_SLOT + ucol + wave * RW * WS_LDF;
-          const float* const xs = X + hv * FVW + col;  // this lane's columns of the virtual segment
-          // training forward (Zout): the row also goes to HBM for the weight
-          // gradient, with non-temporal stores as spmm_kernel's
-          float* const zrow = Zout ? Zout + rw0 * ldz + (int64_t)s * F + hv * FVW + col : nullptr;
-          auto flush = [&](int r, const float4& v) {  // r: the wave's row
-            if (col_ok) {
-              *reinterpret_cast<float4*>(dst + r * WS_LDF) = v;
-              if (zrow && r < nvalid) {
-                f32x4_t t = {v.x, v.y, v.z, v.w};
-                __builtin_nontemporal_store(t, reinterpret_cast<f32x4_t*>(zrow + (int64_t)r * ldz));
-              }
-            }
-          };
-          if (s < hs) {
-            // identity block of A_pre (robust_gcn.py:58-65): the rows' own features, SC rows at a time
-            // (a rolled loop: unrolled, the rows' loads and uniform DropEdge hashes crowd the registers)
-#pragma unroll 1
-            for (int i0 = 0; i0 < RW; i0 += SC) {
-              float4 xv[SC];
-#pragma unroll
-              for (int i = 0; i < SC; ++i)
-                xv[i] = (i0 + i < nvalid && rw0 + i0 + i < self_rows && col_ok)
-                            ? *reinterpret_cast<const float4*>(xs + (self_row0 + rw0 + i0 + i) * ldx) : zero4();
-              if (!claim()) return;
-#pragma unroll
-              for (int i = 0; i < SC; ++i) {
-                float w = 1.0f;
-                if (de.active && de.drop_self) w = dropedge_weight(de, 1.0f, self_base + (uint64_t)(rw0 + i0 + i));
-                flush(i0 + i, w != 0.0f ? make_float4(w * xv[i].x, w * xv[i].y, w * xv[i].z, w * xv[i].w) : zero4());
-              }
-            }
-          } else {
-#if GRL_WS_WHATIF & 8
-            // what-if: the MFMA side alone (typed segments are never gathered)
-            if (!claim()) return;
-            for (int r = 0; r < RW; ++r) flush(r, zero4());
-            if (false)
-#endif
-#pragma unroll 1
-            for (int gi = 0; gi < NG; ++gi) {
-              // the next list (next group; else the next segment's first, unless the next virtual part
-              // of this segment re-walks this list) and its first 64 entries load while this one gathers
-              List nxt = cur;
-              if (gi + 1 < NG) {
-                nxt = make_list(rp[NG - 1], s - hs);  // NG <= 2: the next group is the last
-                fetch(nxt, 0, nxt.sidx, nxt.w);
-              } else if (hv + 1 < FV) {
-                if (NG > 1) {
-                  nxt = make_list(rp[0], s - hs);
-                  fetch(nxt, 0, nxt.sidx, nxt.w);
-                }
-              } else if (s + 1 < S) {
-                nxt = make_list(rp[0], s + 1 - hs);
-                fetch(nxt, 0, nxt.sidx, nxt.w);
-              }
-              int row = gi * GR;  // the wave's row being summed
-              int bound = readlane_i(cur.incl, 0);
-              float4 a4 = zero4();
-              for (int c0 = 0; c0 < cur.total; c0 += 64) {
-                int sidx = cur.sidx;
-                float w = cur.w;
-                if (c0 > 0) fetch(cur, c0, sidx, w);  // rows with more than 64 segment edges together
-                uint64_t kept = __ballot(w != 0.0f);
-                while (kept) {
-                  int jj[U];
-#pragma unroll
-                  for (int q = 0; q < U; ++q) {
-                    if (kept) {
-                      jj[q] = __builtin_ctzll(kept);
-                      kept &= kept - 1;
-                    } else {
-                      jj[q] = -1;
-                    }
-                  }
-                  float4 xv[U];
-#pragma unroll
-                  for (int q = 0; q < U; ++q) {
-                    if (jj[q] >= 0) {
-                      const int src = readlane_i(sidx, jj[q]);
-                      // the source row's address is wave-uniform: a scalar base + the lane's column
-                      // offset (global_load's saddr form, no 64-bit VALU add per gathered row)
-                      // (src, ldx >= 0 and ldx < 2^30: an unsigned 32 x 32 -> 64-bit product of bytes)
-                      const uint64_t ra = reinterpret_cast<uint64_t>(X + hv * FVW) +
-                                          (uint64_t)(uint32_t)src * (uint32_t)(ldx * 4);
-                      typedef __attribute__((address_space(1))) const float gfloat;
-                      typedef __attribute__((address_space(1))) const f32x4_t gvec4;
-                      gfloat* const rowp = (gfloat*)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)(ra >> 32)) << 32) |
-                                                     (uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)ra));
-                      xv[q] = zero4();
-                      if (col_ok) {
-                        // C > 256: streaming loads, so the gathered rows (no reuse to speak of in L2) evict
-                        // less of W's 11 MB of planes (1.3 % at F = C = 512, profiles/r05_ab_wide_ntx.txt)
-                        const f32x4_t t = PROD == 4 ? __builtin_nontemporal_load((gvec4*)(rowp + col))
-                                                    : *(gvec4*)(rowp + col);
-                        xv[q] = make_float4(t[0], t[1], t[2], t[3]);
-                      }
-                    }
-                  }
-#pragma unroll
-                  for (int q = 0; q < U; ++q) {
-                    if (jj[q] >= 0) {
-                      const int pos = c0 + jj[q];
-                      while (pos >= bound) {  // rows finished before this entry (wave-uniform)
-                        if (!claim()) return;
-                        flush(row, a4);
-                        a4 = zero4();
-                        ++row;
-                        bound = readlane_i(cur.incl, row - gi * GR);
-                      }
-                      fma4(a4, readlane_f(w, jj[q]), xv[q]);
-                    }
-                  }
-                }
-              }
-              if (!claim()) return;
-              for (; row < (gi + 1) * GR; ++row) {
-                flush(row, a4);
-                a4 = zero4();
-              }
-              cur = nxt;
-            }
-          }
-          if (lane == 0)
-#pragma unroll
-            for (int q = 0; q < NH; ++q) lds_add_rel(&produced[(u + q) % WS_NB], 1);
-        }
-      }
-    }
-    stamp_out();
-  } else {
-#if GRL_WS_ONLY_ROLE == 1
-    return;
-#endif
-    // =========================== MFMA waves ===========================
-    const int c = wave - PROD;
-    const int l32 = lane & 31, h = lane >> 5;
-    constexpr int WSTEP = CB * 3 * FG_FRAG;     // bf16 between K16 steps of W
-    const int nsteps = S * KS * FV;             // one tile's K16 steps (the W stream's period)
-    // uniform base (SGPRs) + the lane's 16 B: saddr loads
-    const uint16_t* wbase = Wf + (int64_t)(c * WS_CB) * 3 * FG_FRAG;
-    const int loff = lane * 8;
-    auto load_b = [&](bf16x8_t (&bb)[WS_CB][3], int gstep) {
-#if GRL_WS_WHATIF & 1
-      gstep = gstep & 1;  // what-if (timing only): a 2-step W stream that stays in L2
-#endif
-      const uint16_t* w = wbase + (int64_t)gstep * WSTEP;
-#pragma unroll
-      for (int j = 0; j < WS_CB; ++j)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) bb[j][q] = *reinterpret_cast<const bf16x8_t*>(w + (j * 3 + q) * FG_FRAG + loff);
-    };
-    f32x16 acc[2][WS_CB];  // [row block][column block]
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < WS_CB; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    // 12 MFMAs of row block i against both column blocks
-    auto mma = [&](int i, const bf16x8_t (&b)[WS_CB][3], const bf16x8_t (&a)[3]) {
-#pragma unroll
-      for (int j = 0; j < WS_CB; ++j) x6_mfma(acc[i][j], a, b[j]);
-    };
-    // this lane's 8 k (step ks) of row i*32 + l32 of a fp32 ring unit
-    auto read_a = [&](const float* zs, int ks, int i, float4& v0, float4& v1) {
-      const float* ar = zs + (i * 32 + l32) * WS_LDF + ks * 16 + h * 8;
-      v0 = *reinterpret_cast<const float4*>(ar);
-      v1 = *reinterpret_cast<const float4*>(ar + 4);
-    };
-    auto split_a = [&](const float4& v0, const float4& v1, bf16x8_t (&a)[3]) {
-#if GRL_WS_WHATIF & 2
-      a[0] = __builtin_bit_cast(bf16x8_t, make_uint4(__float_as_uint(v0.x), __float_as_uint(v0.y), __float_as_uint(v1.x), __float_as_uint(v1.y)));
-      a[1] = __builtin_bit_cast(bf16x8_t, make_uint4(__float_as_uint(v0.z), __float_as_uint(v0.w), __float_as_uint(v1.z), __float_as_uint(v1.w)));
-      a[2] = a[0];  // what-if (timing only): no split VALU
-      return;
-#endif
-      uint2 p0, p1, p2, r0, r1, r2;
-      split3(v0, p0, p1, p2);
-      split3(v1, r0, r1, r2);
-      a[0] = __builtin_bit_cast(bf16x8_t, make_uint4(p0.x, p0.y, r0.x, r0.y));
-      a[1] = __builtin_bit_cast(bf16x8_t, make_uint4(p1.x, p1.y, r1.x, r1.y));
-      a[2] = __builtin_bit_cast(bf16x8_t, make_uint4(p2.x, p2.y, r2.x, r2.y));
-    };
-    // scheduling hint for the region just written: 2 MFMAs, then 3 VALU / 1 MFMA
-    auto interleave = [&]() {
-      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-#pragma unroll
-      for (int q = 0; q < 10; ++q) {
-        __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-      }
-    };
-    bf16x8_t bb[2][WS_CB][3];
-    int nxt = 0;  // K16 step (within the tile) of the next W fragments to load
-    load_b(bb[0], nxt);
-    nxt = nxt + 1 == nsteps ? 0 : nxt + 1;
-    int u = 0;
-    for (int64_t tile = blockIdx.x; tile < num_tiles; tile += gridDim.x) {
-      for (int su = 0; su < S * FV * NH; ++su, ++u) {
-        const int slot = u % WS_NB, g = u / WS_NB;
-        const float* zs = ring + slot * WS_SLOT;
-        if (!wait_ge(&produced[slot], PROD * (g + 1), &waited, spin_limit, status)) return;
-#if GRL_WS_WHATIF & 4
-        if (lane == 0) lds_add_rel(&consumed[slot], 1);  // what-if: the gather alone
-        continue;
-#endif
-        // Software-pipelined by row block: the split of the next row block's
-        // A fragments (VALU) is interleaved with the current row block's 12
-        // MFMAs (an MFMA holds the SIMD's issue for 8 of its 32 cycles; the
-        // VALU fits in the rest), instead of running between them.
-        bf16x8_t pa[2][3];
-        {
-          float4 v0, v1;
-          read_a(zs, 0, 0, v0, v1);
-          split_a(v0, v1, pa[0]);
-        }
-#pragma unroll
-        for (int ks = 0; ks < KSU; ++ks) {  // KSU is even: the stage of step ks is ks & 1
-          load_b(bb[(ks + 1) & 1], nxt);
-          nxt = nxt + 1 == nsteps ? 0 : nxt + 1;
-          const int st = ks & 1;
-          float4 v0, v1;
-          read_a(zs, ks, 1, v0, v1);
-          __builtin_amdgcn_sched_barrier(0);
-          mma(0, bb[st], pa[0]);
-          split_a(v0, v1, pa[1]);
-          interleave();
-          __builtin_amdgcn_sched_barrier(0);
-          if (ks + 1 < KSU) read_a(zs, ks + 1, 0, v0, v1);
-          __builtin_amdgcn_sched_barrier(0);
-          mma(1, bb[st], pa[1]);
-          if (ks + 1 < KSU) split_a(v0, v1, pa[0]);
-          interleave();
-          __builtin_amdgcn_sched_barrier(0);
-        }
-        // the slot's A fragments are in registers once their reads returned
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (lane == 0) lds_add_rel(&consumed[slot], 1);
-      }
-      // tile done: bias + ReLU, as gemm_x6_kernel
-      const int64_t m0 = tile * WS_R;
-      const bool epi = bias != nullptr || relu;
-      if (m0 + WS_R <= M) {  // whole tile (wave-uniform): row offsets are uniform multiples of C
-#pragma unroll
-        for (int j = 0; j < WS_CB; ++j) {
-          const int n = (c * WS_CB + j) * 32 + l32;
-          const float bv = (bias && n < C) ? bias[n] : 0.0f;
-          float* const o = out + (m0 + 4 * h) * C + n;
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              float v = acc[i][j][r];
-              if (epi) {
-                v = v + bv;
-                if (relu) v = v > 0.0f ? v : 0.0f;
-              }
-              if (n < C) o[(int64_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * C] = v;
-              acc[i][j][r] = 0.0f;
-            }
-        }
-        continue;
-      }
-#pragma unroll
-      for (int j = 0; j < WS_CB; ++j) {
-        const int n = (c * WS_CB + j) * 32 + l32;
-        const float bv = (bias && n < C) ? bias[n] : 0.0f;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            if (m < M && n < C) {
-              float v = acc[i][j][r];
-              if (epi) {
-                v = v + bv;
-                if (relu) v = v > 0.0f ? v : 0.0f;
-              }
-              out[m * C + n] = v;
-            }
-            acc[i][j][r] = 0.0f;
-          }
-      }
-    }
-    stamp_out();
-  }
+// The forward over a bf16 table (grl_graphconv_fwd_bf16, _fwd_train_bf16): X
+// holds bf16 bits, ldx counts them.  No data-gradient form (its gathered
+// operand is the fp32 gradient).
+template <int KS, bool VALS, int FV = 1, int PROD = 8>
+__global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_bf16_kernel(
+    int64_t M, int L, int hs, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+    const float* __restrict__ vals, uint64_t edge_base, uint64_t self_base, const uint16_t* __restrict__ X,
+    int64_t ldx, const uint16_t* __restrict__ Wf, const float* __restrict__ bias, int relu,
+    float* __restrict__ out, int C, DropDev de, int64_t num_tiles, float* __restrict__ Zout, int64_t ldz,
+    int spin_limit, int* __restrict__ status, int64_t self_row0) {
+  constexpr bool EID = false;
+  const int32_t* const eid = nullptr;
+  const int64_t self_rows = M;
+#define GRL_WS_BF16 1
+#include "graphconv_ws_body.inc"
+#undef GRL_WS_BF16
 }
 
 }  // namespace
@@ -945,7 +575,9 @@ static int ws_spin_limit() {
 // return GRL_E_TIMEOUT itself, as round 3's entry points did.
 __device__ int g_grl_sticky;  // WS_WHO_* bits of the calls whose outputs were poisoned
 
-constexpr int WS_WHO_FWD = 1, WS_WHO_FWD_TRAIN = 2, WS_WHO_BWD_DATA = 4;
+constexpr int WS_WHO_FWD = 1, WS_WHO_FWD_TRAIN = 2, WS_WHO_BWD_DATA = 4, WS_WHO_FWD_BF16 = 8,
+              WS_WHO_FWD_TRAIN_BF16 = 16;
+constexpr int WS_WHO_COUNT = 5;
 
 __global__ void ws_poison_kernel(const int* __restrict__ status, float* __restrict__ a, int64_t na,
                                  float* __restrict__ b, int64_t nb, int who) {
@@ -957,8 +589,11 @@ __global__ void ws_poison_kernel(const int* __restrict__ status, float* __restri
 }
 
 static const char* who_name(int who) {
-  return who == WS_WHO_FWD ? "grl_graphconv_fwd" : who == WS_WHO_FWD_TRAIN ? "grl_graphconv_fwd_train"
-                                                                          : "grl_graphconv_bwd_data";
+  return who == WS_WHO_FWD               ? "grl_graphconv_fwd"
+         : who == WS_WHO_FWD_TRAIN       ? "grl_graphconv_fwd_train"
+         : who == WS_WHO_BWD_DATA        ? "grl_graphconv_bwd_data"
+         : who == WS_WHO_FWD_BF16        ? "grl_graphconv_fwd_bf16"
+                                         : "grl_graphconv_fwd_train_bf16";
 }
 
 static int graphconv_status(const int* status, float* a, int64_t na, float* b, int64_t nb, hipStream_t st, int who) {
@@ -1021,9 +656,51 @@ static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M
 #undef GRL_WS_ARGS
 }
 
-static int graphconv_fused_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int F, const float* W,
+// The same for a bf16 table (graphconv_ws_bf16_kernel: the forward only).
+static void launch_ws_bf16(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M, int L, int hs,
+                           const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, const uint16_t* Wf,
+                           const float* bias, int relu, float* out, DropDev d, int64_t tiles, float* Z, int64_t ldz,
+                           int spin, int* status) {
+#define GRL_WS_ARGS                                                                                                \
+  grid, dim3(64 * WS_WAVES), 0, st, M, L, hs, g->rowptr, g->colidx, g->vals, g->edge_id_base, g->self_id_base, X, \
+      ldx, Wf, bias, relu, out, C, d, tiles, Z, ldz, spin, status, g->self_row0
+#define GRL_WS_ONE(KS_, FV_, PROD_)                                                                                \
+  do {                                                                                                            \
+    if (v)                                                                                                        \
+      hipLaunchKernelGGL((graphconv_ws_bf16_kernel<KS_, true, FV_, PROD_>), GRL_WS_ARGS);                         \
+    else                                                                                                          \
+      hipLaunchKernelGGL((graphconv_ws_bf16_kernel<KS_, false, FV_, PROD_>), GRL_WS_ARGS);                        \
+  } while (0)
+#define GRL_WS_PRODS(KS_, FV_)       \
+  do {                               \
+    if (C <= 256)                    \
+      GRL_WS_ONE(KS_, FV_, 8);       \
+    else                             \
+      GRL_WS_ONE(KS_, FV_, 4);       \
+  } while (0)
+#ifdef GRL_WS_DIAG_ONE
+  GRL_WS_ONE(16, GRL_WS_DIAG_FV, GRL_WS_DIAG_PROD);
+#else
+  switch (F) {
+    case 64: GRL_WS_PRODS(4, 1); break;
+    case 128: GRL_WS_PRODS(8, 1); break;
+    case 256: GRL_WS_PRODS(16, 1); break;
+    case 512: GRL_WS_PRODS(16, 2); break;
+    default: GRL_WS_PRODS(16, 4); break;  // 1024
+  }
+#endif
+#undef GRL_WS_PRODS
+#undef GRL_WS_ONE
+#undef GRL_WS_ARGS
+}
+
+// XT = float: X is the fp32 table; XT = uint16_t: bf16 bits, always on the
+// persistent kernel (there is no bf16 phase-alternating kernel).
+template <typename XT>
+static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, const float* W,
                                const float* bias, int C, int relu, float* out, const GrlDropEdge* de, void* ws,
                                hipStream_t st, float* Z = nullptr) {
+  constexpr bool BF16 = std::is_same<XT, uint16_t>::value;
   const int hs = g->has_self ? 1 : 0;
   const int64_t K = (int64_t)segments(g) * F;
   uint16_t* Wf = static_cast<uint16_t*>(ws);
@@ -1038,19 +715,25 @@ static int graphconv_fused_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx
   const DropDev d = to_dev(de);
   const bool v = g->vals != nullptr;
   // the persistent kernel (Z out, wide shapes and row-range views: only it)
-  if (opt(OPT_FG_WS) != 0 || Z || F > 256 || C > 256 || g->self_row0 != 0) {
+  if (BF16 || opt(OPT_FG_WS) != 0 || Z || F > 256 || C > 256 || g->self_row0 != 0) {
     const int64_t ldz = K;
     const int64_t ws_tiles = ceil_div(M, WS_R);
     const int64_t grid = std::min<int64_t>(ws_tiles, (int64_t)device_cu_count());
     int* status = ws_status(ws, K, C);
     const int spin = ws_spin_limit();
     GRL_HIP(hipMemsetAsync(status, 0, sizeof(int), st));
-    launch_ws<false>(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu, out, d,
-                     ws_tiles, Z, ldz, nullptr, M, spin, status);
+    if constexpr (BF16)
+      launch_ws_bf16(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu, out, d,
+                     ws_tiles, Z, ldz, spin, status);
+    else
+      launch_ws<false>(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu, out, d,
+                       ws_tiles, Z, ldz, nullptr, M, spin, status);
     GRL_LAUNCH_CHECK();
-    return graphconv_status(status, out, M * C, Z, M * ldz, st, Z ? WS_WHO_FWD_TRAIN : WS_WHO_FWD);
+    return graphconv_status(status, out, M * C, Z, M * ldz, st,
+                            BF16 ? (Z ? WS_WHO_FWD_TRAIN_BF16 : WS_WHO_FWD_BF16) : (Z ? WS_WHO_FWD_TRAIN : WS_WHO_FWD));
   }
-#define GRL_FUSED_LAUNCH(KS_)                                                                                        \
+  if constexpr (!BF16) {
+#define GRL_FUSED_LAUNCH(KS_)                                                                                      \
   do {                                                                                                               \
     if (v)                                                                                                           \
       hipLaunchKernelGGL((graphconv_fused_kernel<KS_, true>), dim3((unsigned)tiles), dim3(256), 0, st, M,            \
@@ -1068,6 +751,7 @@ static int graphconv_fused_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx
   else
     GRL_FUSED_LAUNCH(4);
 #undef GRL_FUSED_LAUNCH
+  }
   GRL_LAUNCH_CHECK();
   return GRL_OK;
 }
@@ -1124,6 +808,16 @@ static bool fused_path(const GrlTypedCsr* g, const float* X, int64_t ldx, int F,
          (!g->split || g->split->num_heavy == 0);
 }
 
+// The same rule for a bf16 table (grl_graphconv_fwd_bf16, _fwd_train_bf16):
+// a lane loads its 4 columns as 8 B, so X is 8 B-aligned with ldx % 4 == 0,
+// and the row bytes ldx * 2 fit 32 bits.
+static bool fused_path_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, const float* W, int C) {
+  return graphconv_fused_enabled() && graphconv_fused_shape_ok(F, C, g->num_types) &&
+         x6_path_ok(g->num_rows, g->path_rows, C, (int64_t)segments(g) * F) &&
+         al16(W) && C % 4 == 0 && reinterpret_cast<uintptr_t>(X) % 8 == 0 && ldx % 4 == 0 && ldx < (1LL << 31) &&
+         (!g->split || g->split->num_heavy == 0);
+}
+
 // The data gradient of one GraphConv layer by reassociation (see grl.h):
 // dX = sum_s (A_drop,s^T G) W_s^T on the one-kernel GraphConv over the typed
 // transpose.  Eligible when the shape is (grl_graphconv_bwd_data_shape_ok) and
@@ -1137,7 +831,7 @@ static bool bwd_data_path(const GrlTypedCsr* gt, const float* G, int64_t ldg, in
 
 // What grl_graphconv_fwd and _fwd_train check alike (`outs`: their outputs are
 // non-NULL); *K = the linear's depth, set for a graph with rows.
-static int graphconv_fwd_check(const char* who, const GrlTypedCsr* g, const float* X, int64_t ldx, int F,
+static int graphconv_fwd_check(const char* who, const GrlTypedCsr* g, const void* X, int64_t ldx, int F,
                                const float* W, int C, bool outs, const void* ws, int32_t* K) {
   const int rc = csr_fwd_check(who, g, F, ldx, X && W && outs);
   if (rc) return rc;
@@ -1228,6 +922,54 @@ extern "C" int grl_graphconv_fwd_train(const GrlTypedCsr* g, const float* X, int
   if (fused_path(g, X, ldx, F, W, C) && al16(Z) && workspace && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
     return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, workspace, as_stream(stream), Z);
   rc = grl_typed_spmm_fwd(g, X, ldx, F, Z, de, stream);
+  return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, g->num_rows, K, C, relu, g->path_rows, workspace,
+                                     workspace_bytes, stream);
+}
+
+// ---- the forward over a bf16 feature table (X: bf16 bits; W, bias, out, Z fp32) ----
+extern "C" size_t grl_graphconv_fwd_bf16_workspace_query(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx,
+                                                        int32_t F, const float* W, int32_t C) {
+  if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0) return 0;
+  const int64_t K = (int64_t)segments(g) * F;
+  if (K > 2147483647LL) return 0;
+  if (fused_path_bf16(g, X, ldx, F, W, C)) return graphconv_fused_ws_bytes(K, C);
+  return graphconv_two_kernel_ws(g, F, C);
+}
+
+extern "C" int grl_graphconv_fwd_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F, const float* W,
+                                      const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
+                                      void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  TraceRange trace_("grl_graphconv_fwd_bf16");
+  int32_t K = 0;
+  int rc = graphconv_fwd_check("grl_graphconv_fwd_bf16", g, X, ldx, F, W, C, out != nullptr, workspace, &K);
+  if (rc || g->num_rows == 0) return rc;
+  const int64_t M = g->num_rows;
+  char* ws = static_cast<char*>(workspace);
+  if (fused_path_bf16(g, X, ldx, F, W, C) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, ws, as_stream(stream));
+  // Z whole in the workspace, then the linear (its workspace behind Z); no row-chunked form
+  const size_t need = graphconv_two_kernel_ws(g, F, C);
+  if (!ws || workspace_bytes < need)
+    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_fwd_bf16: workspace %zu < %zu", workspace_bytes, need);
+  const size_t zfull = ws_align((size_t)M * (size_t)K * 4);
+  float* Z = reinterpret_cast<float*>(ws);
+  rc = grl_typed_spmm_fwd_bf16(g, X, ldx, F, 0, Z, K, F, de, stream);
+  if (rc) return rc;
+  return grl_linear_fwd_ex(Z, K, W, 0, bias, out, M, K, C, relu, g->path_rows, ws + zfull, workspace_bytes - zfull,
+                           stream);
+}
+
+extern "C" int grl_graphconv_fwd_train_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+                                            const float* W, const float* bias, int32_t C, int32_t relu, float* out,
+                                            float* Z, const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
+                                            grl_stream_t stream) {
+  TraceRange trace_("grl_graphconv_fwd_train_bf16");
+  int32_t K = 0;
+  int rc = graphconv_fwd_check("grl_graphconv_fwd_train_bf16", g, X, ldx, F, W, C, out && Z, workspace, &K);
+  if (rc || g->num_rows == 0) return rc;
+  if (fused_path_bf16(g, X, ldx, F, W, C) && al16(Z) && workspace && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, workspace, as_stream(stream), Z);
+  rc = grl_typed_spmm_fwd_bf16(g, X, ldx, F, 0, Z, K, F, de, stream);
   return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, g->num_rows, K, C, relu, g->path_rows, workspace,
                                      workspace_bytes, stream);
 }
@@ -1329,10 +1071,11 @@ extern "C" int grl_check(grl_stream_t stream) {
   GRL_HIP(hipStreamSynchronize(st));
   const int h = *reinterpret_cast<volatile int*>(word);
   if (h == 0) return GRL_OK;
-  GRL_FAIL(GRL_E_TIMEOUT, "%s%s%s%s%s: a wave of the persistent GraphConv kernel gave up waiting on its LDS ring "
-           "(bound %d sleeps); those calls' outputs were set to NaN",
-           (h & WS_WHO_FWD) ? "grl_graphconv_fwd" : "", (h & WS_WHO_FWD) && (h & ~WS_WHO_FWD) ? ", " : "",
-           (h & WS_WHO_FWD_TRAIN) ? "grl_graphconv_fwd_train" : "",
-           (h & WS_WHO_FWD_TRAIN) && (h & WS_WHO_BWD_DATA) ? ", " : "",
-           (h & WS_WHO_BWD_DATA) ? "grl_graphconv_bwd_data" : "", ws_spin_limit());
+  char names[160];
+  size_t n = 0;
+  names[0] = 0;
+  for (int i = 0; i < WS_WHO_COUNT; ++i)
+    if (h & (1 << i)) n += snprintf(names + n, sizeof(names) - n, "%s%s", n ? ", " : "", who_name(1 << i));
+  GRL_FAIL(GRL_E_TIMEOUT, "%s: a wave of the persistent GraphConv kernel gave up waiting on its LDS ring "
+           "(bound %d sleeps); those calls' outputs were set to NaN", names, ws_spin_limit());
 }

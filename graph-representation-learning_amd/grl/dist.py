@@ -873,6 +873,16 @@ def _p2p_exchange(sends, recvs, group):
     return works, finish
 
 
+def _require_fp32_table(X_ext: torch.Tensor, who: str) -> None:
+    """The row-pipelined and streamed sharded layers take fp32 features only
+    (grl.ops' layer entries also read a bf16 table; these layers' backward and
+    halo tables are written for fp32)."""
+    if X_ext.dtype != torch.float32:
+        from ._lib import GrlError
+
+        raise GrlError(f"{who}: features and weights must be float32 (got {X_ext.dtype})")
+
+
 def _all_agree(flag: bool, group, device) -> bool:
     """True iff `flag` holds on every rank of `group` (a MIN all-reduce): a
     decision that picks between two different collective sequences must be
@@ -956,6 +966,7 @@ class _RowPipelinedGraphConv(torch.autograd.Function):
 
         with trace("grl.rows_pipeline_fwd"):
             X_ext = sg.exchange_table(X_loc)
+            _require_fp32_table(X_ext, "rows-pipelined GraphConv")
             graph = sg.graph.with_dropedge(dropedge)
             Wc, bc = W.contiguous(), b.contiguous() if b is not None else None
             row0 = sg.plan.row_begin
@@ -1449,6 +1460,7 @@ class ShardedGraph:
 
         p = self.plan
         X_ext = self.exchange_table(X_loc)
+        _require_fp32_table(X_ext, "streamed GraphConv")
         W, b = layer.h_weights, layer.bias
         C = W.shape[1]
         T = self._stream_table(C, X_ext)

@@ -49,18 +49,23 @@ def _de_ref(graph):
 _TABLE_DTYPES = (torch.float32, torch.bfloat16)
 
 
+def _bf16_suffix(X2: torch.Tensor) -> str:
+    """'_bf16' for a bfloat16 table: the grl_graphconv_fwd*_bf16 entries."""
+    return "_bf16" if X2.dtype == torch.bfloat16 else ""
+
+
 def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: bool = False):
     """The checked operands of a forward over `graph` -- (X2, F, Wc, bc, out,
     Z): the features' 2-D row view and width, the contiguous weights
     [segments * F, C] and bias (None without), out [num_rows, C] (with
     weights) and Z [num_rows, segments * F] (want_Z), each the contiguous
-    fp32 tensor given or a new one.  Without weights (the aggregation alone)
-    the features may be bfloat16."""
+    fp32 tensor given or a new one.  The features may be bfloat16 (the table
+    is read as stored); weights and bias are float32."""
     _require_device(X, "node features")
-    if W is None and X.dtype not in _TABLE_DTYPES:
-        raise _lib.GrlError(f"node features must be float32 or bfloat16 (got {X.dtype})")
-    if W is not None and (X.dtype != torch.float32 or W.dtype != torch.float32):
-        raise _lib.GrlError(f"{who}: features and weights must be float32")
+    if X.dtype not in _TABLE_DTYPES:
+        raise _lib.GrlError(f"{who}: node features must be float32 or bfloat16 (got {X.dtype})")
+    if W is not None and (W.dtype != torch.float32 or (b is not None and b.dtype != torch.float32)):
+        raise _lib.GrlError(f"{who}: weights and bias must be float32")
     X2 = _rows_view(X)
     if X2.shape[0] != graph.num_cols:
         raise _lib.GrlError(f"features have {X2.shape[0]} rows, graph gathers from {graph.num_cols}")
@@ -483,7 +488,9 @@ def graph_conv_bwd_data_rows(g: torch.Tensor, graph: TypedGraph, W: torch.Tensor
 class _GraphConv(torch.autograd.Function):
     """One GraphConv layer, X -> Z = A_drop X -> out = Z W + b [ReLU]
     (robust_gcn.py:45-51), as one autograd node: the same kernels and
-    results as typed_aggregate + graph_linear.  (Running dW on a second HIP
+    results as typed_aggregate + graph_linear.  X float32 or bfloat16 (the
+    bf16-table forward entries; the backward is the fp32 layer's on the fp32
+    Z and output gradient, dX rounded once to X's dtype).  (Running dW on a second HIP
     stream beside dZ / the transposed gather was measured and bought nothing:
     39-41 ms per C3 layer either way, each kernel already fills the chip.)"""
 
@@ -499,7 +506,7 @@ class _GraphConv(torch.autograd.Function):
             out = graph_conv_infer(X, graph, Wc, bc, relu)
         else:  # one kernel that also writes Z where it applies (grl_graphconv_fwd_train)
             out, Z = graph_conv_fwd_train(X, graph, Wc, bc, relu)
-        ctx.graph, ctx.relu, ctx.has_b, ctx.xshape = graph, relu, b is not None, X.shape
+        ctx.graph, ctx.relu, ctx.has_b, ctx.xshape, ctx.xdtype = graph, relu, b is not None, X.shape, X.dtype
         ctx.recompute = recompute
         # recompute: keep X (F wide) instead of Z ((L+1)F wide); the backward
         # regenerates Z with the same DropEdge record, so it is the same bits
@@ -512,9 +519,10 @@ class _GraphConv(torch.autograd.Function):
         want_w = ctx.needs_input_grad[2]
         want_b = ctx.has_b and ctx.needs_input_grad[3]
         g, mask, db_pre = relu_grad(g.contiguous().float(), out if ctx.relu else None, want_b)
-        if ctx.recompute and ctx.needs_input_grad[0] and want_w:
+        if ctx.recompute and ctx.needs_input_grad[0] and want_w and ctx.xdtype == torch.float32:
             # X was kept, not Z: the one-kernel data gradient also writes G_s = A_drop,s^T g and
-            # dW_s = Z_s^T g = X^T G_s -- no re-aggregation of Z (same products, another order)
+            # dW_s = Z_s^T g = X^T G_s -- no re-aggregation of Z (same products, another order).
+            # (X^T G_s is an fp32 GEMM: a bf16 X re-aggregates Z below instead of being widened.)
             res = graph_conv_bwd_data(g, ctx.graph, W, ctx.xshape[-1], mask, want_aggregate=True)
             if res is not None:
                 dX, G_agg, g_eff = res
@@ -535,7 +543,7 @@ class _GraphConv(torch.autograd.Function):
                 dZ = linear_bwd_data(g, mask, W)
                 dX = spmm_backward(dZ, ctx.graph, F)
                 del dZ
-            dX = dX.view(ctx.xshape)
+            dX = dX.view(ctx.xshape).to(ctx.xdtype)  # a bf16 X: the fp32 dX rounded once
         if want_w or (want_b and db_pre is None):
             dW, db = linear_bwd_weight(Z, g, mask, want_b and db_pre is None)
         if db_pre is not None:
@@ -549,12 +557,13 @@ def graph_conv_fwd_train(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=
     one-kernel path writes Z as a by-product (for the backward's dW); the
     result is bitwise spmm_forward then linear_fwd.  out / Z: contiguous
     [num_rows, C] / [num_rows, segments * F] fp32 tensors to write (e.g. the
-    row block of a streamed layer)."""
+    row block of a streamed layer).  X float32, or bfloat16 read as stored
+    (grl_graphconv_fwd_train_bf16): out and Z bitwise the call's on X.float()."""
     X2, F, Wc, bc, out, Z = _forward_args("graph_conv_fwd_train", X, graph, W, b, out, Z, want_Z=True)
     K, C = Wc.shape
     ws_bytes = _lib.lib().grl_linear_fwd_ex_workspace_size(graph.num_rows, K, C, graph.path_rows)
     ws = _workspace(ws_bytes, X.device)
-    call("grl_graphconv_fwd_train", ctypes.byref(graph.csr_c(F)), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(),
+    call("grl_graphconv_fwd_train" + _bf16_suffix(X2), ctypes.byref(graph.csr_c(F)), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(),
          _ptr(bc), C, int(relu), out.data_ptr(), Z.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes,
          current_stream_handle(X.device))
     return out, Z
@@ -567,16 +576,21 @@ def graph_conv_infer(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None
     and Z never reaches HBM; otherwise Z lives only in the call's workspace
     and max_workspace_bytes bounds it (the call then works in row chunks,
     bitwise equal to the whole-graph result).  out: a contiguous
-    [num_rows, C] float32 tensor to write (e.g. a row block of a halo table)."""
+    [num_rows, C] float32 tensor to write (e.g. a row block of a halo table).
+    X float32, or bfloat16 read as stored (grl_graphconv_fwd_bf16: out bitwise
+    the call's on X.float(); one kernel where X is 8 B-aligned with a row
+    stride that is a multiple of 4, else Z whole in the workspace -- the bf16
+    entry has no row-chunked form, so a max_workspace_bytes below that raises)."""
     X2, F, Wc, bc, out, _ = _forward_args("graph_conv_infer", X, graph, W, b, out)
     C = Wc.shape[1]
     csr = graph.csr_c(F)
+    sfx = _bf16_suffix(X2)
     # the fused one-kernel path needs only W's planes; else Z whole
-    full = _lib.lib().grl_graphconv_fwd_workspace_query(ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F,
-                                                         Wc.data_ptr(), C)
+    query = getattr(_lib.lib(), f"grl_graphconv_fwd{sfx}_workspace_query")
+    full = query(ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), C)
     ws_bytes = full if max_workspace_bytes is None else min(full, int(max_workspace_bytes))
     ws = _workspace(ws_bytes, X.device)
-    call("grl_graphconv_fwd", ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc), C,
+    call("grl_graphconv_fwd" + sfx, ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc), C,
          int(relu), out.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes, current_stream_handle(X.device))
     return out
 
@@ -605,14 +619,19 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
     saved-Z path's.  Peak memory in the G_s form: the transient G_agg
     [num_cols, (L+1) C] of the backward is Z-sized when C == F, so recompute
     lowers the memory held BETWEEN the passes, not the backward's peak.
-    A bfloat16 X (fp32 W, b) runs typed_aggregate then graph_linear, two
-    autograd nodes: the one-kernel GraphConv kernels take fp32 features only.
-    out is bitwise the layer's on X.float(), dW and db those of its saved-Z
-    path, X.grad that path's dX rounded to bfloat16."""
-    if X.dtype == torch.bfloat16:
-        if W.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
-            raise _lib.GrlError("graph_conv: weights and bias must be float32")
-        return graph_linear(typed_aggregate(X, graph), W, b, relu, getattr(graph, "path_rows", 0))
+    A bfloat16 X (fp32 W, b) is the same one autograd node on the bf16-table
+    entries (grl_graphconv_fwd_bf16, _fwd_train_bf16: the one-kernel layer
+    gathering half the bytes; no widened copy of X is made).  out is bitwise
+    the layer's on X.float(); the backward is that layer's on the fp32 Z and
+    output gradient, so dW and db are those of its saved-Z path and X.grad is
+    its dX rounded once to bfloat16.  With recompute=True the bf16 X is what
+    is kept, and the backward re-aggregates Z from it (the bf16 SpMM, the
+    same bits): it does not take the dW_s = X^T G_s form, which needs an
+    fp32 X, so dW and db stay bitwise the saved-Z path's."""
+    if X.dtype not in _TABLE_DTYPES:
+        raise _lib.GrlError(f"graph_conv: node features must be float32 or bfloat16 (got {X.dtype})")
+    if W.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
+        raise _lib.GrlError("graph_conv: weights and bias must be float32")
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (X, W, b))):
         if isinstance(graph, EdgeBlockedGraph):  # one int32 CSR per call: aggregate by blocks, then the linear
             return linear_fwd(spmm_forward(X, graph), W.contiguous(), b.contiguous() if b is not None else None,

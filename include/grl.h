@@ -405,6 +405,41 @@ int grl_graphconv_fwd_train(const GrlTypedCsr* g, const float* X, int64_t ldx,
                             const GrlDropEdge* de, void* workspace,
                             size_t workspace_bytes, grl_stream_t stream);
 
+/* grl_graphconv_fwd / _fwd_train / _fwd_workspace_query over a feature table
+ * stored as bf16 bits (as grl_typed_spmm_fwd_bf16 takes it; ldx counted in
+ * bf16 elements).  W, bias, out and Z are fp32; the checks and error codes
+ * are the fp32 entries'.  Widening bf16 is exact and every Z element runs the
+ * fp32 kernels' fmaf chain, so out and Z are bitwise what the fp32 entries
+ * give on the widened table, at half the gather bytes.
+ * One kernel (the persistent warp-specialised form only: its gather waves
+ * load a lane's 4 columns as 8 B and widen them at the fmaf; ring, MFMA
+ * waves and epilogue are the fp32 kernel's) where grl_graphconv_fwd's rule
+ * holds with the table's alignment restated: X 8 B-aligned, ldx % 4 == 0,
+ * ldx < 2^31.  The workspace query then returns the size of W's planes.
+ * Elsewhere grl_typed_spmm_fwd_bf16 into Z, then grl_linear_fwd_ex with
+ * g->path_rows: the training entry writes the caller's Z (workspace as
+ * grl_graphconv_fwd_train); the inference entry keeps Z whole in the
+ * workspace (the query's size; smaller: GRL_E_WORKSPACE -- there is no
+ * row-chunked form).  graphconv_fused = 0 and ws_spin apply as to the fp32
+ * entries; a bounded wait that runs out poisons out (and Z) and is reported
+ * by grl_check() under these entries' own names.  The data gradient is the
+ * fp32 layer's (grl_graphconv_bwd_data on the fp32 output gradient).       */
+size_t grl_graphconv_fwd_bf16_workspace_query(const GrlTypedCsr* g,
+                                              const uint16_t* X, int64_t ldx,
+                                              int32_t F, const float* W,
+                                              int32_t C);
+int grl_graphconv_fwd_bf16(const GrlTypedCsr* g, const uint16_t* X,
+                           int64_t ldx, int32_t F, const float* W,
+                           const float* bias, int32_t C, int32_t relu,
+                           float* out, const GrlDropEdge* de, void* workspace,
+                           size_t workspace_bytes, grl_stream_t stream);
+int grl_graphconv_fwd_train_bf16(const GrlTypedCsr* g, const uint16_t* X,
+                                 int64_t ldx, int32_t F, const float* W,
+                                 const float* bias, int32_t C, int32_t relu,
+                                 float* out, float* Z, const GrlDropEdge* de,
+                                 void* workspace, size_t workspace_bytes,
+                                 grl_stream_t stream);
+
 /* Data gradient of one GraphConv layer in ONE kernel.  Replaces the
  * autograd chain MmBackward0 (dZ = G W^T, robust_gcn.py:50) then
  * BmmBackward0 (dX = A_drop^T dZ, robust_gcn.py:45) by its reassociation
