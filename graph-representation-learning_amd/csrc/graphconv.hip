@@ -615,23 +615,35 @@ static int graphconv_status(const int* status, float* a, int64_t na, float* b, i
 }
 
 // One launch of the persistent kernel for gathered width F and output width
-// C: the template instance for (F, C > 256) with or without edge values /
-// eid (the data-gradient form); grid = one workgroup per CU (at most the
-// tiles).
-template <bool EID>
+// C over a table of XT (float, or uint16_t: bf16 bits): the template instance
+// for (F, C > 256) with or without edge values / eid (the data-gradient form,
+// fp32 only); grid = one workgroup per CU (at most the tiles).  The bf16
+// kernel has no eid / self_rows arguments.
+template <typename XT, bool EID>
 static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M, int L, int hs,
-                      const GrlTypedCsr* g, const float* X, int64_t ldx, const uint16_t* Wf, const float* bias,
+                      const GrlTypedCsr* g, const XT* X, int64_t ldx, const uint16_t* Wf, const float* bias,
                       int relu, float* out, DropDev d, int64_t tiles, float* Z, int64_t ldz, const int32_t* eid,
                       int64_t self_rows, int spin, int* status) {
-#define GRL_WS_ARGS                                                                                                \
+  constexpr bool BF16 = std::is_same<XT, uint16_t>::value;
+  static_assert(!(BF16 && EID), "no data-gradient form over a bf16 table");
+#define GRL_WS_HEAD                                                                                                \
   grid, dim3(64 * WS_WAVES), 0, st, M, L, hs, g->rowptr, g->colidx, g->vals, g->edge_id_base, g->self_id_base, X, \
-      ldx, Wf, bias, relu, out, C, d, tiles, Z, ldz, eid, self_rows, spin, status, g->self_row0
-#define GRL_WS_ONE(KS_, FV_, PROD_)                                                                                \
+      ldx, Wf, bias, relu, out, C, d, tiles, Z, ldz
+#define GRL_WS_INST(KS_, VALS_, FV_, PROD_)                                                                       \
   do {                                                                                                            \
-    if (v)                                                                                                        \
-      hipLaunchKernelGGL((graphconv_ws_kernel<KS_, true, EID, FV_, PROD_>), GRL_WS_ARGS);                         \
+    if constexpr (BF16)                                                                                           \
+      hipLaunchKernelGGL((graphconv_ws_bf16_kernel<KS_, VALS_, FV_, PROD_>), GRL_WS_HEAD, spin, status,           \
+                         g->self_row0);                                                                           \
     else                                                                                                          \
-      hipLaunchKernelGGL((graphconv_ws_kernel<KS_, false, EID, FV_, PROD_>), GRL_WS_ARGS);                        \
+      hipLaunchKernelGGL((graphconv_ws_kernel<KS_, VALS_, EID, FV_, PROD_>), GRL_WS_HEAD, eid, self_rows, spin,   \
+                         status, g->self_row0);                                                                   \
+  } while (0)
+#define GRL_WS_ONE(KS_, FV_, PROD_)        \
+  do {                                     \
+    if (v)                                 \
+      GRL_WS_INST(KS_, true, FV_, PROD_);  \
+    else                                   \
+      GRL_WS_INST(KS_, false, FV_, PROD_); \
   } while (0)
 #define GRL_WS_PRODS(KS_, FV_)       \
   do {                               \
@@ -653,45 +665,8 @@ static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M
 #endif
 #undef GRL_WS_PRODS
 #undef GRL_WS_ONE
-#undef GRL_WS_ARGS
-}
-
-// The same for a bf16 table (graphconv_ws_bf16_kernel: the forward only).
-static void launch_ws_bf16(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M, int L, int hs,
-                           const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, const uint16_t* Wf,
-                           const float* bias, int relu, float* out, DropDev d, int64_t tiles, float* Z, int64_t ldz,
-                           int spin, int* status) {
-#define GRL_WS_ARGS                                                                                                \
-  grid, dim3(64 * WS_WAVES), 0, st, M, L, hs, g->rowptr, g->colidx, g->vals, g->edge_id_base, g->self_id_base, X, \
-      ldx, Wf, bias, relu, out, C, d, tiles, Z, ldz, spin, status, g->self_row0
-#define GRL_WS_ONE(KS_, FV_, PROD_)                                                                                \
-  do {                                                                                                            \
-    if (v)                                                                                                        \
-      hipLaunchKernelGGL((graphconv_ws_bf16_kernel<KS_, true, FV_, PROD_>), GRL_WS_ARGS);                         \
-    else                                                                                                          \
-      hipLaunchKernelGGL((graphconv_ws_bf16_kernel<KS_, false, FV_, PROD_>), GRL_WS_ARGS);                        \
-  } while (0)
-#define GRL_WS_PRODS(KS_, FV_)       \
-  do {                               \
-    if (C <= 256)                    \
-      GRL_WS_ONE(KS_, FV_, 8);       \
-    else                             \
-      GRL_WS_ONE(KS_, FV_, 4);       \
-  } while (0)
-#ifdef GRL_WS_DIAG_ONE
-  GRL_WS_ONE(16, GRL_WS_DIAG_FV, GRL_WS_DIAG_PROD);
-#else
-  switch (F) {
-    case 64: GRL_WS_PRODS(4, 1); break;
-    case 128: GRL_WS_PRODS(8, 1); break;
-    case 256: GRL_WS_PRODS(16, 1); break;
-    case 512: GRL_WS_PRODS(16, 2); break;
-    default: GRL_WS_PRODS(16, 4); break;  // 1024
-  }
-#endif
-#undef GRL_WS_PRODS
-#undef GRL_WS_ONE
-#undef GRL_WS_ARGS
+#undef GRL_WS_INST
+#undef GRL_WS_HEAD
 }
 
 // XT = float: X is the fp32 table; XT = uint16_t: bf16 bits, always on the
@@ -722,12 +697,8 @@ static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, i
     int* status = ws_status(ws, K, C);
     const int spin = ws_spin_limit();
     GRL_HIP(hipMemsetAsync(status, 0, sizeof(int), st));
-    if constexpr (BF16)
-      launch_ws_bf16(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu, out, d,
-                     ws_tiles, Z, ldz, spin, status);
-    else
-      launch_ws<false>(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu, out, d,
-                       ws_tiles, Z, ldz, nullptr, M, spin, status);
+    launch_ws<XT, false>(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu, out, d,
+                         ws_tiles, Z, ldz, nullptr, M, spin, status);
     GRL_LAUNCH_CHECK();
     return graphconv_status(status, out, M * C, Z, M * ldz, st,
                             BF16 ? (Z ? WS_WHO_FWD_TRAIN_BF16 : WS_WHO_FWD_BF16) : (Z ? WS_WHO_FWD_TRAIN : WS_WHO_FWD));
@@ -780,8 +751,8 @@ static int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, c
   int* status = ws_status(ws, K, Cout);
   const int spin = ws_spin_limit();
   GRL_HIP(hipMemsetAsync(status, 0, sizeof(int), st));
-  launch_ws<true>(Cin, Cout, v, dim3((unsigned)grid), st, M, gt->num_types, hs, gt, G, ldg, Wf, nullptr, 0, dX, d,
-                  ws_tiles, Gagg, K, eid, self_rows, spin, status);
+  launch_ws<float, true>(Cin, Cout, v, dim3((unsigned)grid), st, M, gt->num_types, hs, gt, G, ldg, Wf, nullptr, 0, dX,
+                         d, ws_tiles, Gagg, K, eid, self_rows, spin, status);
   GRL_LAUNCH_CHECK();
   return graphconv_status(status, dX, M * Cout, Gagg, M * K, st, WS_WHO_BWD_DATA);
 }
@@ -798,24 +769,17 @@ static size_t graphconv_two_kernel_ws(const GrlTypedCsr* g, int F, int C) {
 
 // grl_graphconv_fwd takes the fused kernel when its arithmetic equals the
 // two-kernel path's (the linear on the x6 GEMM: large graphs, 16-B aligned W,
-// C % 4 == 0), the shapes fit it (graphconv_fused_shape_ok), X rows are
-// float4-aligned and no heavy row is split (the split path sums chunk
-// partials, a different order).
-static bool fused_path(const GrlTypedCsr* g, const float* X, int64_t ldx, int F, const float* W, int C) {
+// C % 4 == 0), the shapes fit it (graphconv_fused_shape_ok), every row of X
+// (XT = float, or uint16_t: bf16 bits) is aligned to the one load of a lane's
+// 4 columns (16 B / 8 B) and its bytes fit 32 bits (the gather's row offset),
+// and no heavy row is split (the split path sums chunk partials, a different
+// order).
+template <typename XT>
+static bool fused_path(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, const float* W, int C) {
   return graphconv_fused_enabled() && graphconv_fused_shape_ok(F, C, g->num_types) &&
-         x6_path_ok(g->num_rows, g->path_rows, C, (int64_t)segments(g) * F) &&
-         al16(W) && C % 4 == 0 && al16(X) && ldx % 4 == 0 && ldx < (1LL << 30) &&  // gather: 32-bit row bytes
-         (!g->split || g->split->num_heavy == 0);
-}
-
-// The same rule for a bf16 table (grl_graphconv_fwd_bf16, _fwd_train_bf16):
-// a lane loads its 4 columns as 8 B, so X is 8 B-aligned with ldx % 4 == 0,
-// and the row bytes ldx * 2 fit 32 bits.
-static bool fused_path_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, const float* W, int C) {
-  return graphconv_fused_enabled() && graphconv_fused_shape_ok(F, C, g->num_types) &&
-         x6_path_ok(g->num_rows, g->path_rows, C, (int64_t)segments(g) * F) &&
-         al16(W) && C % 4 == 0 && reinterpret_cast<uintptr_t>(X) % 8 == 0 && ldx % 4 == 0 && ldx < (1LL << 31) &&
-         (!g->split || g->split->num_heavy == 0);
+         x6_path_ok(g->num_rows, g->path_rows, C, (int64_t)segments(g) * F) && al16(W) && C % 4 == 0 &&
+         reinterpret_cast<uintptr_t>(X) % (4 * sizeof(XT)) == 0 && ldx % 4 == 0 &&
+         ldx < (int64_t)((1ULL << 32) / sizeof(XT)) && (!g->split || g->split->num_heavy == 0);
 }
 
 // The data gradient of one GraphConv layer by reassociation (see grl.h):
@@ -848,13 +812,102 @@ static int graphconv_fwd_check(const char* who, const GrlTypedCsr* g, const void
 
 using namespace grl;
 
-extern "C" size_t grl_graphconv_fwd_workspace_query(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F,
-                                                   const float* W, int32_t C) {
+// ---- the forward, written once for an fp32 table (XT = float) and a table of
+// bf16 bits (XT = uint16_t; W, bias, out and Z are fp32 either way) ----------
+// Z [num_rows, segments * F] = A_drop X: the first kernel of the two-kernel chain
+static int spmm_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, float* Z, const GrlDropEdge* de,
+                    grl_stream_t stream) {
+  return grl_typed_spmm_fwd(g, X, ldx, F, Z, de, stream);
+}
+static int spmm_fwd(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F, float* Z, const GrlDropEdge* de,
+                    grl_stream_t stream) {
+  return grl_typed_spmm_fwd_bf16(g, X, ldx, F, 0, Z, (int64_t)segments(g) * F, F, de, stream);
+}
+
+template <typename XT>
+static size_t graphconv_fwd_workspace_query(const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F, const float* W,
+                                            int32_t C) {
   if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0) return 0;
   const int64_t K = (int64_t)segments(g) * F;
   if (K > 2147483647LL) return 0;
   if (fused_path(g, X, ldx, F, W, C)) return graphconv_fused_ws_bytes(K, C);
   return graphconv_two_kernel_ws(g, F, C);
+}
+
+template <typename XT>
+static int graphconv_fwd(const char* who, const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F, const float* W,
+                         const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
+                         void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  TraceRange trace_(who);
+  int32_t K = 0;
+  int rc = graphconv_fwd_check(who, g, X, ldx, F, W, C, out != nullptr, workspace, &K);
+  if (rc || g->num_rows == 0) return rc;
+  const int64_t M = g->num_rows;
+  hipStream_t st = as_stream(stream);
+  char* ws = static_cast<char*>(workspace);
+  if (fused_path(g, X, ldx, F, W, C) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, ws, st);  // one kernel: Z never leaves the CU
+  const size_t need = graphconv_two_kernel_ws(g, F, C);
+  if (ws && workspace_bytes >= need) {
+    // whole graph: Z in the workspace, then the linear (its workspace behind Z)
+    const size_t zfull = ws_align((size_t)M * (size_t)K * 4);
+    float* Z = reinterpret_cast<float*>(ws);
+    rc = spmm_fwd(g, X, ldx, F, Z, de, stream);
+    if (rc) return rc;
+    return grl_linear_fwd_ex(Z, K, W, 0, bias, out, M, K, C, relu, g->path_rows, ws + zfull, workspace_bytes - zfull,
+                             stream);
+  }
+  if constexpr (std::is_same<XT, uint16_t>::value) {
+    GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);  // no row-chunked form
+  } else {
+    // Row chunks: Z for R rows at a time (bounded memory), on the x6 GEMM only,
+    // whose per-element arithmetic does not depend on M -- so the result is
+    // bitwise that of the whole-graph call.
+    const bool x6 = x6_path_ok(M, g->path_rows, C, K) && al16(W) && C % 4 == 0;
+    if (!x6 || (g->split && g->split->num_heavy > 0) || !ws)
+      GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu (row chunking needs the x6 GEMM shape and no heavy-row split "
+               "plan)", who, workspace_bytes, grl_graphconv_fwd_workspace_size(M, g->num_types, g->has_self, F, C));
+    const size_t planes_bytes = ws_align(x6_ws_bytes_p(M, g->path_rows, C, K));
+    const int64_t per_row = (int64_t)K * 4;
+    int64_t R = workspace_bytes > planes_bytes ? (int64_t)((workspace_bytes - planes_bytes) / per_row) : 0;
+    R = R / LB_M * LB_M;
+    if (R < LB_M)
+      GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu holds fewer than %d rows of Z", who, workspace_bytes, LB_M);
+    uint16_t* planes = reinterpret_cast<uint16_t*>(ws);
+    float* Z = reinterpret_cast<float*>(ws + planes_bytes);
+    rc = x6_split_w(W, K, C, planes, st);
+    for (int64_t r0 = 0; r0 < M && !rc; r0 += R) {
+      const int64_t rows = std::min<int64_t>(R, M - r0);
+      rc = spmm_fwd_rows(g, r0, rows, X, ldx, F, Z, de, st);
+      if (!rc) rc = x6_gemm_rows(Z, rows, K, planes, C, bias, relu, out + r0 * C, st);
+    }
+    return rc;
+  }
+}
+
+template <typename XT>
+static int graphconv_fwd_train(const char* who, const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F,
+                               const float* W, const float* bias, int32_t C, int32_t relu, float* out, float* Z,
+                               const GrlDropEdge* de, void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  TraceRange trace_(who);
+  int32_t K = 0;
+  int rc = graphconv_fwd_check(who, g, X, ldx, F, W, C, out && Z, workspace, &K);
+  if (rc || g->num_rows == 0) return rc;
+  if (fused_path(g, X, ldx, F, W, C) && al16(Z) && workspace && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, workspace, as_stream(stream), Z);
+  rc = spmm_fwd(g, X, ldx, F, Z, de, stream);
+  return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, g->num_rows, K, C, relu, g->path_rows, workspace,
+                                     workspace_bytes, stream);
+}
+
+extern "C" size_t grl_graphconv_fwd_workspace_query(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F,
+                                                   const float* W, int32_t C) {
+  return graphconv_fwd_workspace_query(g, X, ldx, F, W, C);
+}
+
+extern "C" size_t grl_graphconv_fwd_bf16_workspace_query(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx,
+                                                        int32_t F, const float* W, int32_t C) {
+  return graphconv_fwd_workspace_query(g, X, ldx, F, W, C);
 }
 
 extern "C" size_t grl_graphconv_fwd_workspace_size(int64_t num_rows, int32_t num_types, int32_t has_self, int32_t F,
@@ -868,110 +921,31 @@ extern "C" size_t grl_graphconv_fwd_workspace_size(int64_t num_rows, int32_t num
 extern "C" int grl_graphconv_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
                                  const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
                                  void* workspace, size_t workspace_bytes, grl_stream_t stream) {
-  TraceRange trace_("grl_graphconv_fwd");
-  int32_t K = 0;
-  int rc = graphconv_fwd_check("grl_graphconv_fwd", g, X, ldx, F, W, C, out != nullptr, workspace, &K);
-  if (rc || g->num_rows == 0) return rc;
-  const int64_t M = g->num_rows;
-  hipStream_t st = as_stream(stream);
-  char* ws = static_cast<char*>(workspace);
-  const size_t zfull = ws_align((size_t)M * (size_t)K * 4);
-  if (fused_path(g, X, ldx, F, W, C) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, ws, st);  // one kernel: Z never leaves the CU
-  if (ws && workspace_bytes >= graphconv_two_kernel_ws(g, F, C)) {
-    // whole graph: Z in the workspace, then the linear (its workspace behind Z)
-    float* Z = reinterpret_cast<float*>(ws);
-    rc = grl_typed_spmm_fwd(g, X, ldx, F, Z, de, stream);
-    if (rc) return rc;
-    return grl_linear_fwd_ex(Z, K, W, 0, bias, out, M, K, C, relu, g->path_rows, ws + zfull, workspace_bytes - zfull,
-                             stream);
-  }
-  // Row chunks: Z for R rows at a time (bounded memory), on the x6 GEMM only,
-  // whose per-element arithmetic does not depend on M -- so the result is
-  // bitwise that of the whole-graph call.
-  const bool x6 = x6_path_ok(M, g->path_rows, C, K) && al16(W) && C % 4 == 0;
-  if (!x6 || (g->split && g->split->num_heavy > 0) || !ws)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_fwd: workspace %zu < %zu (row chunking needs the x6 GEMM shape and no "
-             "heavy-row split plan)", workspace_bytes,
-             grl_graphconv_fwd_workspace_size(M, g->num_types, g->has_self, F, C));
-  const size_t planes_bytes = ws_align(x6_ws_bytes_p(M, g->path_rows, C, K));
-  const int64_t per_row = (int64_t)K * 4;
-  int64_t R = workspace_bytes > planes_bytes ? (int64_t)((workspace_bytes - planes_bytes) / per_row) : 0;
-  R = R / LB_M * LB_M;
-  if (R < LB_M)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_fwd: workspace %zu holds fewer than %d rows of Z", workspace_bytes, LB_M);
-  uint16_t* planes = reinterpret_cast<uint16_t*>(ws);
-  float* Z = reinterpret_cast<float*>(ws + planes_bytes);
-  rc = x6_split_w(W, K, C, planes, st);
-  for (int64_t r0 = 0; r0 < M && !rc; r0 += R) {
-    const int64_t rows = std::min<int64_t>(R, M - r0);
-    rc = spmm_fwd_rows(g, r0, rows, X, ldx, F, Z, de, st);
-    if (!rc) rc = x6_gemm_rows(Z, rows, K, planes, C, bias, relu, out + r0 * C, st);
-  }
-  return rc;
+  return graphconv_fwd("grl_graphconv_fwd", g, X, ldx, F, W, bias, C, relu, out, de, workspace, workspace_bytes,
+                       stream);
+}
+
+extern "C" int grl_graphconv_fwd_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F, const float* W,
+                                      const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
+                                      void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  return graphconv_fwd("grl_graphconv_fwd_bf16", g, X, ldx, F, W, bias, C, relu, out, de, workspace, workspace_bytes,
+                       stream);
 }
 
 extern "C" int grl_graphconv_fwd_train(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
                                        const float* bias, int32_t C, int32_t relu, float* out, float* Z,
                                        const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
                                        grl_stream_t stream) {
-  TraceRange trace_("grl_graphconv_fwd_train");
-  int32_t K = 0;
-  int rc = graphconv_fwd_check("grl_graphconv_fwd_train", g, X, ldx, F, W, C, out && Z, workspace, &K);
-  if (rc || g->num_rows == 0) return rc;
-  if (fused_path(g, X, ldx, F, W, C) && al16(Z) && workspace && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, workspace, as_stream(stream), Z);
-  rc = grl_typed_spmm_fwd(g, X, ldx, F, Z, de, stream);
-  return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, g->num_rows, K, C, relu, g->path_rows, workspace,
-                                     workspace_bytes, stream);
-}
-
-// ---- the forward over a bf16 feature table (X: bf16 bits; W, bias, out, Z fp32) ----
-extern "C" size_t grl_graphconv_fwd_bf16_workspace_query(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx,
-                                                        int32_t F, const float* W, int32_t C) {
-  if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0) return 0;
-  const int64_t K = (int64_t)segments(g) * F;
-  if (K > 2147483647LL) return 0;
-  if (fused_path_bf16(g, X, ldx, F, W, C)) return graphconv_fused_ws_bytes(K, C);
-  return graphconv_two_kernel_ws(g, F, C);
-}
-
-extern "C" int grl_graphconv_fwd_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F, const float* W,
-                                      const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
-                                      void* workspace, size_t workspace_bytes, grl_stream_t stream) {
-  TraceRange trace_("grl_graphconv_fwd_bf16");
-  int32_t K = 0;
-  int rc = graphconv_fwd_check("grl_graphconv_fwd_bf16", g, X, ldx, F, W, C, out != nullptr, workspace, &K);
-  if (rc || g->num_rows == 0) return rc;
-  const int64_t M = g->num_rows;
-  char* ws = static_cast<char*>(workspace);
-  if (fused_path_bf16(g, X, ldx, F, W, C) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, ws, as_stream(stream));
-  // Z whole in the workspace, then the linear (its workspace behind Z); no row-chunked form
-  const size_t need = graphconv_two_kernel_ws(g, F, C);
-  if (!ws || workspace_bytes < need)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_fwd_bf16: workspace %zu < %zu", workspace_bytes, need);
-  const size_t zfull = ws_align((size_t)M * (size_t)K * 4);
-  float* Z = reinterpret_cast<float*>(ws);
-  rc = grl_typed_spmm_fwd_bf16(g, X, ldx, F, 0, Z, K, F, de, stream);
-  if (rc) return rc;
-  return grl_linear_fwd_ex(Z, K, W, 0, bias, out, M, K, C, relu, g->path_rows, ws + zfull, workspace_bytes - zfull,
-                           stream);
+  return graphconv_fwd_train("grl_graphconv_fwd_train", g, X, ldx, F, W, bias, C, relu, out, Z, de, workspace,
+                             workspace_bytes, stream);
 }
 
 extern "C" int grl_graphconv_fwd_train_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
                                             const float* W, const float* bias, int32_t C, int32_t relu, float* out,
                                             float* Z, const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
                                             grl_stream_t stream) {
-  TraceRange trace_("grl_graphconv_fwd_train_bf16");
-  int32_t K = 0;
-  int rc = graphconv_fwd_check("grl_graphconv_fwd_train_bf16", g, X, ldx, F, W, C, out && Z, workspace, &K);
-  if (rc || g->num_rows == 0) return rc;
-  if (fused_path_bf16(g, X, ldx, F, W, C) && al16(Z) && workspace && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, workspace, as_stream(stream), Z);
-  rc = grl_typed_spmm_fwd_bf16(g, X, ldx, F, 0, Z, K, F, de, stream);
-  return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, g->num_rows, K, C, relu, g->path_rows, workspace,
-                                     workspace_bytes, stream);
+  return graphconv_fwd_train("grl_graphconv_fwd_train_bf16", g, X, ldx, F, W, bias, C, relu, out, Z, de, workspace,
+                             workspace_bytes, stream);
 }
 
 extern "C" int32_t grl_graphconv_bwd_data_shape_ok(int64_t rows, int32_t num_types, int32_t has_self, int32_t C,
