@@ -6,6 +6,12 @@
 // products a_i b_j with i + j <= 2 on v_mfma_f32_32x32x16_bf16 with fp32
 // accumulation.  The kernels that must agree bitwise (the one-kernel GraphConv
 // and the SpMM + GEMM chain) agree because they share these functions.
+// That every kernel issues each of the six products, from the right planes
+// at every fragment and staging slot, is checked on inputs where one product
+// sum decides each output element, within 2^-22 of the float64 product:
+// tests/test_gpu_x6_planes.py (the numpy model of the six products and the
+// proof that a single wrong product breaks the bound: tests/x6_isolate.py,
+// tests/test_x6_isolate.py).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -10,22 +10,7 @@ values, independent of the GPU."""
 import numpy as np
 import pytest
 
-
-def bf16_rne(x: np.ndarray) -> np.ndarray:
-    """fp32 -> bf16 (round to nearest even) -> fp32, as v_cvt_pk_bf16_f32."""
-    u = x.astype(np.float32).view(np.uint32).astype(np.uint64)
-    r = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
-    return r.astype(np.uint32).view(np.float32)
-
-
-def split3(v: np.ndarray):
-    v = v.astype(np.float32)
-    v0 = bf16_rne(v)
-    r1 = (v - v0).astype(np.float32)
-    v1 = bf16_rne(r1)
-    r2 = (r1 - v1).astype(np.float32)
-    v2 = bf16_rne(r2)
-    return v0, v1, v2
+from x6_isolate import bf16_rne, split3  # the numpy split, shared with the plane-isolating tests
 
 
 def _values(rng, n, lo=-96, hi=100):
