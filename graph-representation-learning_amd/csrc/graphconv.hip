@@ -15,7 +15,11 @@
 //  * graphconv_ws_bf16_kernel: graphconv_ws_kernel over a table of bf16 bits
 //    (grl_graphconv_fwd_bf16, _fwd_train_bf16): the same body text
 //    (graphconv_ws_body.inc) with 8 B-per-lane gather loads widened at the
-//    fmaf, bitwise the fp32 kernel on the widened table.
+//    fmaf, bitwise the fp32 kernel on the widened table;
+//  * graphconv_ws_bf16o_kernel: graphconv_ws_bf16_kernel writing bf16 rows
+//    with a caller-given stride (grl_graphconv_fwd_bf16_to_bf16,
+//    _fwd_train_bf16_to_bf16): the epilogue rounds the finished tile to
+//    nearest even in registers and stores two columns per dword.
 // Shared pieces: the gather sums a wave's rows' segment-t neighbour rows
 // (one float4 per lane, one 1 KB row per wave-instruction, the rows' edge
 // lists streamed as one list with flushes at row boundaries); the multiply
@@ -507,7 +511,9 @@ __global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_kernel(
     const int32_t* __restrict__ eid, int64_t self_rows, int spin_limit, int* __restrict__ status,
     int64_t self_row0) {
 #define GRL_WS_BF16 0
+#define GRL_WS_OUT16 0
 #include "graphconv_ws_body.inc"
+#undef GRL_WS_OUT16
 #undef GRL_WS_BF16
 }
 
@@ -525,7 +531,48 @@ __global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_bf16_kernel(
   const int32_t* const eid = nullptr;
   const int64_t self_rows = M;
 #define GRL_WS_BF16 1
+#define GRL_WS_OUT16 0
 #include "graphconv_ws_body.inc"
+#undef GRL_WS_OUT16
+#undef GRL_WS_BF16
+}
+
+// GRL_WS_OUT16_PACK: the bf16-output kernel's store form, 1 = lane pairs trade
+// a value and store dwords, 0 = one 2 B store per element (the same bits; the
+// A/B is in DESIGN.md §4.17)
+#ifndef GRL_WS_OUT16_PACK
+#define GRL_WS_OUT16_PACK 1
+#endif
+
+// two fp32 -> one dword of two bf16 (lo in bits 15:0), each rounded to nearest even
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+// lane l ^ 1's value (a DPP move within the quad, no LDS)
+__device__ __forceinline__ float swap_lane_pair(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));  // quad_perm [1, 0, 3, 2]
+}
+
+// The bf16-table forward writing bf16 rows (grl_graphconv_fwd_bf16_to_bf16,
+// _fwd_train_bf16_to_bf16): graphconv_ws_bf16_kernel but for the epilogue's
+// stores -- out holds bf16 bits, ldo (>= C, counted in bf16 elements) apart a
+// row, each the fp32 epilogue value rounded to nearest even.  Zout stays fp32.
+template <int KS, bool VALS, int FV = 1, int PROD = 8>
+__global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_bf16o_kernel(
+    int64_t M, int L, int hs, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+    const float* __restrict__ vals, uint64_t edge_base, uint64_t self_base, const uint16_t* __restrict__ X,
+    int64_t ldx, const uint16_t* __restrict__ Wf, const float* __restrict__ bias, int relu,
+    uint16_t* __restrict__ out, int C, DropDev de, int64_t num_tiles, float* __restrict__ Zout, int64_t ldz,
+    int spin_limit, int* __restrict__ status, int64_t self_row0, int64_t ldo) {
+  constexpr bool EID = false;
+  const int32_t* const eid = nullptr;
+  const int64_t self_rows = M;
+#define GRL_WS_BF16 1
+#define GRL_WS_OUT16 1
+#include "graphconv_ws_body.inc"
+#undef GRL_WS_OUT16
 #undef GRL_WS_BF16
 }
 
@@ -576,8 +623,8 @@ static int ws_spin_limit() {
 __device__ int g_grl_sticky;  // WS_WHO_* bits of the calls whose outputs were poisoned
 
 constexpr int WS_WHO_FWD = 1, WS_WHO_FWD_TRAIN = 2, WS_WHO_BWD_DATA = 4, WS_WHO_FWD_BF16 = 8,
-              WS_WHO_FWD_TRAIN_BF16 = 16;
-constexpr int WS_WHO_COUNT = 5;
+              WS_WHO_FWD_TRAIN_BF16 = 16, WS_WHO_FWD_BF16_TO_BF16 = 32, WS_WHO_FWD_TRAIN_BF16_TO_BF16 = 64;
+constexpr int WS_WHO_COUNT = 7;
 
 __global__ void ws_poison_kernel(const int* __restrict__ status, float* __restrict__ a, int64_t na,
                                  float* __restrict__ b, int64_t nb, int who) {
@@ -588,20 +635,44 @@ __global__ void ws_poison_kernel(const int* __restrict__ status, float* __restri
     (i < na ? a[i] : b[i - na]) = nan;
 }
 
-static const char* who_name(int who) {
-  return who == WS_WHO_FWD               ? "grl_graphconv_fwd"
-         : who == WS_WHO_FWD_TRAIN       ? "grl_graphconv_fwd_train"
-         : who == WS_WHO_BWD_DATA        ? "grl_graphconv_bwd_data"
-         : who == WS_WHO_FWD_BF16        ? "grl_graphconv_fwd_bf16"
-                                         : "grl_graphconv_fwd_train_bf16";
+// ws_poison_kernel for a strided bf16 out [M, C] (ldo apart a row): a bf16 NaN
+// into C of every ldo elements, never the columns beside them; b (Z) as there.
+__global__ void ws_poison_bf16_kernel(const int* __restrict__ status, uint16_t* __restrict__ a, int64_t M, int C,
+                                      int64_t ldo, float* __restrict__ b, int64_t nb, int who) {
+  if (*status == 0) return;
+  if (blockIdx.x == 0 && threadIdx.x == 0) __hip_atomic_fetch_or(&g_grl_sticky, who, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const float nan = __builtin_nanf("");
+  const int64_t na = M * C;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < na + nb; i += (int64_t)gridDim.x * blockDim.x) {
+    if (i < na)
+      a[(i / C) * ldo + i % C] = 0x7fc0;
+    else
+      b[i - na] = nan;
+  }
 }
 
-static int graphconv_status(const int* status, float* a, int64_t na, float* b, int64_t nb, hipStream_t st, int who) {
+static const char* who_name(int who) {
+  return who == WS_WHO_FWD                 ? "grl_graphconv_fwd"
+         : who == WS_WHO_FWD_TRAIN         ? "grl_graphconv_fwd_train"
+         : who == WS_WHO_BWD_DATA          ? "grl_graphconv_bwd_data"
+         : who == WS_WHO_FWD_BF16          ? "grl_graphconv_fwd_bf16"
+         : who == WS_WHO_FWD_TRAIN_BF16    ? "grl_graphconv_fwd_train_bf16"
+         : who == WS_WHO_FWD_BF16_TO_BF16  ? "grl_graphconv_fwd_bf16_to_bf16"
+                                           : "grl_graphconv_fwd_train_bf16_to_bf16";
+}
+
+// a: the call's out, float [M, C] contiguous or uint16_t (bf16 bits) [M, C] with row stride ldo
+template <typename OT>
+static int graphconv_status(const int* status, OT* a, int64_t M, int C, int64_t ldo, float* b, int64_t nb,
+                            hipStream_t st, int who) {
   const bool sync = opt(OPT_WS_STATUS_SYNC) != 0;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (sync) GRL_HIP(hipStreamIsCapturing(st, &cs));
   if (!sync || cs != hipStreamCaptureStatusNone) {
-    hipLaunchKernelGGL(ws_poison_kernel, dim3(1024), dim3(256), 0, st, status, a, na, b, b ? nb : 0, who);
+    if constexpr (std::is_same<OT, uint16_t>::value)
+      hipLaunchKernelGGL(ws_poison_bf16_kernel, dim3(1024), dim3(256), 0, st, status, a, M, C, ldo, b, b ? nb : 0, who);
+    else
+      hipLaunchKernelGGL(ws_poison_kernel, dim3(1024), dim3(256), 0, st, status, a, M * C, b, b ? nb : 0, who);
     GRL_LAUNCH_CHECK();
     return GRL_OK;
   }
@@ -618,20 +689,27 @@ static int graphconv_status(const int* status, float* a, int64_t na, float* b, i
 // C over a table of XT (float, or uint16_t: bf16 bits): the template instance
 // for (F, C > 256) with or without edge values / eid (the data-gradient form,
 // fp32 only); grid = one workgroup per CU (at most the tiles).  The bf16
-// kernel has no eid / self_rows arguments.
-template <typename XT, bool EID>
+// kernels have no eid / self_rows arguments.  OT = uint16_t: out holds bf16
+// bits with row stride ldo (graphconv_ws_bf16o_kernel; the forward over a bf16
+// table only); OT = float: out is [M, C] contiguous and ldo is not looked at.
+template <typename XT, bool EID, typename OT = float>
 static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M, int L, int hs,
                       const GrlTypedCsr* g, const XT* X, int64_t ldx, const uint16_t* Wf, const float* bias,
-                      int relu, float* out, DropDev d, int64_t tiles, float* Z, int64_t ldz, const int32_t* eid,
-                      int64_t self_rows, int spin, int* status) {
+                      int relu, OT* out, int64_t ldo, DropDev d, int64_t tiles, float* Z, int64_t ldz,
+                      const int32_t* eid, int64_t self_rows, int spin, int* status) {
   constexpr bool BF16 = std::is_same<XT, uint16_t>::value;
+  constexpr bool OUT16 = std::is_same<OT, uint16_t>::value;
   static_assert(!(BF16 && EID), "no data-gradient form over a bf16 table");
+  static_assert(!OUT16 || (BF16 && !EID), "bf16 output: the forward over a bf16 table only");
 #define GRL_WS_HEAD                                                                                                \
   grid, dim3(64 * WS_WAVES), 0, st, M, L, hs, g->rowptr, g->colidx, g->vals, g->edge_id_base, g->self_id_base, X, \
       ldx, Wf, bias, relu, out, C, d, tiles, Z, ldz
 #define GRL_WS_INST(KS_, VALS_, FV_, PROD_)                                                                       \
   do {                                                                                                            \
-    if constexpr (BF16)                                                                                           \
+    if constexpr (OUT16)                                                                                          \
+      hipLaunchKernelGGL((graphconv_ws_bf16o_kernel<KS_, VALS_, FV_, PROD_>), GRL_WS_HEAD, spin, status,          \
+                         g->self_row0, ldo);                                                                      \
+    else if constexpr (BF16)                                                                                      \
       hipLaunchKernelGGL((graphconv_ws_bf16_kernel<KS_, VALS_, FV_, PROD_>), GRL_WS_HEAD, spin, status,           \
                          g->self_row0);                                                                           \
     else                                                                                                          \
@@ -670,12 +748,15 @@ static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M
 }
 
 // XT = float: X is the fp32 table; XT = uint16_t: bf16 bits, always on the
-// persistent kernel (there is no bf16 phase-alternating kernel).
-template <typename XT>
+// persistent kernel (there is no bf16 phase-alternating kernel).  OT =
+// uint16_t (a bf16 table only): out holds bf16 bits, ldo apart a row.
+template <typename XT, typename OT>
 static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, const float* W,
-                               const float* bias, int C, int relu, float* out, const GrlDropEdge* de, void* ws,
-                               hipStream_t st, float* Z = nullptr) {
+                               const float* bias, int C, int relu, OT* out, int64_t ldo, const GrlDropEdge* de,
+                               void* ws, hipStream_t st, float* Z = nullptr) {
   constexpr bool BF16 = std::is_same<XT, uint16_t>::value;
+  constexpr bool OUT16 = std::is_same<OT, uint16_t>::value;
+  static_assert(!OUT16 || BF16, "bf16 output: a bf16 table only");
   const int hs = g->has_self ? 1 : 0;
   const int64_t K = (int64_t)segments(g) * F;
   uint16_t* Wf = static_cast<uint16_t*>(ws);
@@ -697,11 +778,13 @@ static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, i
     int* status = ws_status(ws, K, C);
     const int spin = ws_spin_limit();
     GRL_HIP(hipMemsetAsync(status, 0, sizeof(int), st));
-    launch_ws<XT, false>(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu, out, d,
-                         ws_tiles, Z, ldz, nullptr, M, spin, status);
+    launch_ws<XT, false, OT>(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu, out,
+                             ldo, d, ws_tiles, Z, ldz, nullptr, M, spin, status);
     GRL_LAUNCH_CHECK();
-    return graphconv_status(status, out, M * C, Z, M * ldz, st,
-                            BF16 ? (Z ? WS_WHO_FWD_TRAIN_BF16 : WS_WHO_FWD_BF16) : (Z ? WS_WHO_FWD_TRAIN : WS_WHO_FWD));
+    return graphconv_status(status, out, M, C, ldo, Z, M * ldz, st,
+                            OUT16  ? (Z ? WS_WHO_FWD_TRAIN_BF16_TO_BF16 : WS_WHO_FWD_BF16_TO_BF16)
+                            : BF16 ? (Z ? WS_WHO_FWD_TRAIN_BF16 : WS_WHO_FWD_BF16)
+                                   : (Z ? WS_WHO_FWD_TRAIN : WS_WHO_FWD));
   }
   if constexpr (!BF16) {
 #define GRL_FUSED_LAUNCH(KS_)                                                                                      \
@@ -752,9 +835,9 @@ static int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, c
   const int spin = ws_spin_limit();
   GRL_HIP(hipMemsetAsync(status, 0, sizeof(int), st));
   launch_ws<float, true>(Cin, Cout, v, dim3((unsigned)grid), st, M, gt->num_types, hs, gt, G, ldg, Wf, nullptr, 0, dX,
-                         d, ws_tiles, Gagg, K, eid, self_rows, spin, status);
+                         (int64_t)Cout, d, ws_tiles, Gagg, K, eid, self_rows, spin, status);
   GRL_LAUNCH_CHECK();
-  return graphconv_status(status, dX, M * Cout, Gagg, M * K, st, WS_WHO_BWD_DATA);
+  return graphconv_status(status, dX, M, Cout, (int64_t)Cout, Gagg, M * K, st, WS_WHO_BWD_DATA);
 }
 
 // ---- the layer's dispatch: which kernels a grl_graphconv_* call runs -------
@@ -780,6 +863,43 @@ static bool fused_path(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, co
          x6_path_ok(g->num_rows, g->path_rows, C, (int64_t)segments(g) * F) && al16(W) && C % 4 == 0 &&
          reinterpret_cast<uintptr_t>(X) % (4 * sizeof(XT)) == 0 && ldx % 4 == 0 &&
          ldx < (int64_t)((1ULL << 32) / sizeof(XT)) && (!g->split || g->split->num_heavy == 0);
+}
+
+// The bf16-output entries (grl_graphconv_fwd_bf16_to_bf16, _fwd_train_..)
+// take the one kernel where the bf16-table rule holds and out's rows take the
+// epilogue's dword stores of two columns: out 4 B-aligned, ldo even.
+static bool fused_path_out16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, const float* W, int C,
+                             const uint16_t* out, int64_t ldo) {
+  return fused_path(g, X, ldx, F, W, C) && reinterpret_cast<uintptr_t>(out) % 4 == 0 && ldo % 2 == 0;
+}
+
+// Elsewhere they run the bf16 SpMM, the linear into an fp32 [M, C] scratch,
+// and this: dst[m, c] (ldo apart a row) = src[m, c] rounded to nearest even,
+// the kernel epilogue's conversion, so the bits are the one-kernel form's.
+__global__ void round_rows_bf16_kernel(const float* __restrict__ src, int64_t M, int C, uint16_t* __restrict__ dst,
+                                       int64_t ldo) {
+  const int64_t n = M * C;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    dst[(i / C) * ldo + i % C] = (uint16_t)cvt_pk_bf16(src[i], 0.0f);
+}
+
+static int round_rows_bf16(const float* src, int64_t M, int C, uint16_t* dst, int64_t ldo, hipStream_t st) {
+  const unsigned blocks = (unsigned)std::min<int64_t>(ceil_div(M * C, 256), 8192);
+  hipLaunchKernelGGL(round_rows_bf16_kernel, dim3(blocks), dim3(256), 0, st, src, M, C, dst, ldo);
+  GRL_LAUNCH_CHECK();
+  return GRL_OK;
+}
+
+// the fp32 [M, C] the two-kernel form of a bf16-output entry rounds from
+static size_t out16_scratch_bytes(const GrlTypedCsr* g, int C) { return ws_align((size_t)g->num_rows * (size_t)C * 4); }
+
+// What the bf16-output entries check beyond graphconv_fwd_check (host-side,
+// before any row is looked at).
+static int out16_check(const char* who, const void* X, const void* out, int64_t ldo, int C) {
+  GRL_CHECK_ARG(ldo >= C, "%s: need ldo >= C (ldo=%lld C=%d)", who, (long long)ldo, C);
+  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(X) % 2 == 0 && reinterpret_cast<uintptr_t>(out) % 2 == 0,
+                "%s: X and out hold 2-byte elements and must be 2-B aligned", who);
+  return GRL_OK;
 }
 
 // The data gradient of one GraphConv layer by reassociation (see grl.h):
@@ -824,38 +944,66 @@ static int spmm_fwd(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_
   return grl_typed_spmm_fwd_bf16(g, X, ldx, F, 0, Z, (int64_t)segments(g) * F, F, de, stream);
 }
 
-template <typename XT>
+// The rule of an entry with out of OT (float: [num_rows, C] contiguous, ldo
+// not looked at; uint16_t: bf16 bits, ldo apart a row).
+template <typename XT, typename OT>
+static bool fwd_one_kernel(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, const float* W, int C, const OT* out,
+                           int64_t ldo) {
+  if constexpr (std::is_same<OT, uint16_t>::value)
+    return fused_path_out16(g, X, ldx, F, W, C, out, ldo);
+  else
+    return fused_path(g, X, ldx, F, W, C);
+}
+
+template <typename XT, typename OT = float>
 static size_t graphconv_fwd_workspace_query(const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F, const float* W,
-                                            int32_t C) {
+                                            int32_t C, const OT* out = nullptr, int64_t ldo = 0) {
   if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0) return 0;
   const int64_t K = (int64_t)segments(g) * F;
   if (K > 2147483647LL) return 0;
-  if (fused_path(g, X, ldx, F, W, C)) return graphconv_fused_ws_bytes(K, C);
-  return graphconv_two_kernel_ws(g, F, C);
+  if (fwd_one_kernel(g, X, ldx, F, W, C, out, ldo)) return graphconv_fused_ws_bytes(K, C);
+  return graphconv_two_kernel_ws(g, F, C) + (std::is_same<OT, uint16_t>::value ? out16_scratch_bytes(g, C) : 0);
 }
 
-template <typename XT>
+template <typename XT, typename OT = float>
 static int graphconv_fwd(const char* who, const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F, const float* W,
-                         const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
+                         const float* bias, int32_t C, int32_t relu, OT* out, int64_t ldo, const GrlDropEdge* de,
                          void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  constexpr bool OUT16 = std::is_same<OT, uint16_t>::value;
   TraceRange trace_(who);
   int32_t K = 0;
   int rc = graphconv_fwd_check(who, g, X, ldx, F, W, C, out != nullptr, workspace, &K);
-  if (rc || g->num_rows == 0) return rc;
+  if (rc) return rc;
+  if constexpr (OUT16) {
+    rc = out16_check(who, X, out, ldo, C);
+    if (rc) return rc;
+  }
+  if (g->num_rows == 0) return rc;
   const int64_t M = g->num_rows;
   hipStream_t st = as_stream(stream);
   char* ws = static_cast<char*>(workspace);
-  if (fused_path(g, X, ldx, F, W, C) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, ws, st);  // one kernel: Z never leaves the CU
-  const size_t need = graphconv_two_kernel_ws(g, F, C);
+  if (fwd_one_kernel(g, X, ldx, F, W, C, out, ldo) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, ldo, de, ws, st);  // one kernel: Z stays on the CU
+  const size_t scratch = OUT16 ? out16_scratch_bytes(g, C) : 0;
+  const size_t need = graphconv_two_kernel_ws(g, F, C) + scratch;
   if (ws && workspace_bytes >= need) {
-    // whole graph: Z in the workspace, then the linear (its workspace behind Z)
+    // whole graph: Z in the workspace, then the linear (its workspace behind Z; a bf16 out: into an fp32
+    // [M, C] between the two, rounded into out's rows afterwards)
     const size_t zfull = ws_align((size_t)M * (size_t)K * 4);
     float* Z = reinterpret_cast<float*>(ws);
     rc = spmm_fwd(g, X, ldx, F, Z, de, stream);
     if (rc) return rc;
-    return grl_linear_fwd_ex(Z, K, W, 0, bias, out, M, K, C, relu, g->path_rows, ws + zfull, workspace_bytes - zfull,
-                             stream);
+    float* lin_out;
+    if constexpr (OUT16)
+      lin_out = reinterpret_cast<float*>(ws + zfull);
+    else
+      lin_out = out;
+    rc = grl_linear_fwd_ex(Z, K, W, 0, bias, lin_out, M, K, C, relu, g->path_rows, ws + zfull + scratch,
+                           workspace_bytes - zfull - scratch, stream);
+    if constexpr (OUT16) {
+      if (!rc) rc = round_rows_bf16(lin_out, M, C, out, ldo, st);
+    }
+    return rc;
   }
   if constexpr (std::is_same<XT, uint16_t>::value) {
     GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);  // no row-chunked form
@@ -885,19 +1033,40 @@ static int graphconv_fwd(const char* who, const GrlTypedCsr* g, const XT* X, int
   }
 }
 
-template <typename XT>
+template <typename XT, typename OT = float>
 static int graphconv_fwd_train(const char* who, const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F,
-                               const float* W, const float* bias, int32_t C, int32_t relu, float* out, float* Z,
-                               const GrlDropEdge* de, void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+                               const float* W, const float* bias, int32_t C, int32_t relu, OT* out, int64_t ldo,
+                               float* Z, const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
+                               grl_stream_t stream) {
   TraceRange trace_(who);
   int32_t K = 0;
   int rc = graphconv_fwd_check(who, g, X, ldx, F, W, C, out && Z, workspace, &K);
-  if (rc || g->num_rows == 0) return rc;
-  if (fused_path(g, X, ldx, F, W, C) && al16(Z) && workspace && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, de, workspace, as_stream(stream), Z);
-  rc = spmm_fwd(g, X, ldx, F, Z, de, stream);
-  return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, g->num_rows, K, C, relu, g->path_rows, workspace,
-                                     workspace_bytes, stream);
+  if (rc) return rc;
+  if constexpr (std::is_same<OT, uint16_t>::value) {
+    rc = out16_check(who, X, out, ldo, C);
+    if (rc) return rc;
+  }
+  if (g->num_rows == 0) return rc;
+  if (fwd_one_kernel(g, X, ldx, F, W, C, out, ldo) && al16(Z) && workspace &&
+      workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, ldo, de, workspace, as_stream(stream), Z);
+  if constexpr (std::is_same<OT, uint16_t>::value) {
+    // the linear into an fp32 [M, C] at the head of the workspace, rounded into out's rows
+    const size_t scratch = out16_scratch_bytes(g, C);
+    const size_t need = scratch + grl_linear_fwd_ex_workspace_size(g->num_rows, K, C, g->path_rows);
+    if (!workspace || workspace_bytes < need)
+      GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+    float* lin_out = static_cast<float*>(workspace);
+    rc = spmm_fwd(g, X, ldx, F, Z, de, stream);
+    if (!rc)
+      rc = grl_linear_fwd_ex(Z, K, W, 0, bias, lin_out, g->num_rows, K, C, relu, g->path_rows,
+                             static_cast<char*>(workspace) + scratch, workspace_bytes - scratch, stream);
+    return rc ? rc : round_rows_bf16(lin_out, g->num_rows, C, out, ldo, as_stream(stream));
+  } else {
+    rc = spmm_fwd(g, X, ldx, F, Z, de, stream);
+    return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, g->num_rows, K, C, relu, g->path_rows, workspace,
+                                       workspace_bytes, stream);
+  }
 }
 
 extern "C" size_t grl_graphconv_fwd_workspace_query(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F,
@@ -921,31 +1090,54 @@ extern "C" size_t grl_graphconv_fwd_workspace_size(int64_t num_rows, int32_t num
 extern "C" int grl_graphconv_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
                                  const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
                                  void* workspace, size_t workspace_bytes, grl_stream_t stream) {
-  return graphconv_fwd("grl_graphconv_fwd", g, X, ldx, F, W, bias, C, relu, out, de, workspace, workspace_bytes,
-                       stream);
+  return graphconv_fwd("grl_graphconv_fwd", g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, de, workspace,
+                       workspace_bytes, stream);
 }
 
 extern "C" int grl_graphconv_fwd_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F, const float* W,
                                       const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
                                       void* workspace, size_t workspace_bytes, grl_stream_t stream) {
-  return graphconv_fwd("grl_graphconv_fwd_bf16", g, X, ldx, F, W, bias, C, relu, out, de, workspace, workspace_bytes,
-                       stream);
+  return graphconv_fwd("grl_graphconv_fwd_bf16", g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, de, workspace,
+                       workspace_bytes, stream);
 }
 
 extern "C" int grl_graphconv_fwd_train(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
                                        const float* bias, int32_t C, int32_t relu, float* out, float* Z,
                                        const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
                                        grl_stream_t stream) {
-  return graphconv_fwd_train("grl_graphconv_fwd_train", g, X, ldx, F, W, bias, C, relu, out, Z, de, workspace,
-                             workspace_bytes, stream);
+  return graphconv_fwd_train("grl_graphconv_fwd_train", g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, Z, de,
+                             workspace, workspace_bytes, stream);
 }
 
 extern "C" int grl_graphconv_fwd_train_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
                                             const float* W, const float* bias, int32_t C, int32_t relu, float* out,
                                             float* Z, const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
                                             grl_stream_t stream) {
-  return graphconv_fwd_train("grl_graphconv_fwd_train_bf16", g, X, ldx, F, W, bias, C, relu, out, Z, de, workspace,
-                             workspace_bytes, stream);
+  return graphconv_fwd_train("grl_graphconv_fwd_train_bf16", g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, Z, de,
+                             workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t grl_graphconv_fwd_bf16_to_bf16_workspace_query(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx,
+                                                                int32_t F, const float* W, int32_t C,
+                                                                const uint16_t* out, int64_t ldo) {
+  if (ldo < C) return 0;
+  return graphconv_fwd_workspace_query(g, X, ldx, F, W, C, out, ldo);
+}
+
+extern "C" int grl_graphconv_fwd_bf16_to_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+                                              const float* W, const float* bias, int32_t C, int32_t relu,
+                                              uint16_t* out, int64_t ldo, const GrlDropEdge* de, void* workspace,
+                                              size_t workspace_bytes, grl_stream_t stream) {
+  return graphconv_fwd("grl_graphconv_fwd_bf16_to_bf16", g, X, ldx, F, W, bias, C, relu, out, ldo, de, workspace,
+                       workspace_bytes, stream);
+}
+
+extern "C" int grl_graphconv_fwd_train_bf16_to_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+                                                    const float* W, const float* bias, int32_t C, int32_t relu,
+                                                    uint16_t* out, int64_t ldo, float* Z, const GrlDropEdge* de,
+                                                    void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  return graphconv_fwd_train("grl_graphconv_fwd_train_bf16_to_bf16", g, X, ldx, F, W, bias, C, relu, out, ldo, Z, de,
+                             workspace, workspace_bytes, stream);
 }
 
 extern "C" int32_t grl_graphconv_bwd_data_shape_ok(int64_t rows, int32_t num_types, int32_t has_self, int32_t C,
@@ -1045,7 +1237,7 @@ extern "C" int grl_check(grl_stream_t stream) {
   GRL_HIP(hipStreamSynchronize(st));
   const int h = *reinterpret_cast<volatile int*>(word);
   if (h == 0) return GRL_OK;
-  char names[160];
+  char names[320];
   size_t n = 0;
   names[0] = 0;
   for (int i = 0; i < WS_WHO_COUNT; ++i)

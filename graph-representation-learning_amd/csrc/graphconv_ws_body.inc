@@ -1,7 +1,9 @@
 // The body of the warp-specialised persistent GraphConv kernel, included by
 // graphconv.hip once per kernel, inside the kernel's braces, with
 // GRL_WS_BF16 defined: 0 = graphconv_ws_kernel (X fp32), 1 =
-// graphconv_ws_bf16_kernel (X bf16 bits).  Textual sharing, not a function
+// graphconv_ws_bf16_kernel (X bf16 bits), and GRL_WS_OUT16: 1 (with
+// GRL_WS_BF16 1) = graphconv_ws_bf16o_kernel, whose epilogue alone differs
+// (out holds bf16 bits, ldo apart a row).  Textual sharing, not a function
 // template: the fp32 kernels' machine code is pinned
 // (tests/test_codegen_pin.py); an inlined function template around the body,
 // and a traits class around the loads alone, each moved every one of them,
@@ -431,6 +433,64 @@
       // tile done: bias + ReLU, as gemm_x6_kernel
       const int64_t m0 = tile * WS_R;
       const bool epi = bias != nullptr || relu;
+#if GRL_WS_OUT16
+      // bf16 rows (the fp32 value rounded to nearest even) with the caller's
+      // stride ldo; the two blocks of the fp32 form below -- whole tile, ragged
+      // tile with per-element row bounds -- as one text over WHOLE.
+      // GRL_WS_OUT16_PACK: lanes l and l ^ 1 (columns n, n + 1; C % 4 == 0, so
+      // both or neither are < C) trade one value of each register pair (2p,
+      // 2p + 1: rows m, m + 1); the even lane then stores row m's columns
+      // (n, n + 1) as one dword, the odd lane row m + 1's (n - 1, n): out is
+      // 4 B-aligned and ldo even.  Else one 2 B store per element.
+      auto store_tile = [&](auto whole_c) {
+        constexpr bool WHOLE = decltype(whole_c)::value;
+#pragma unroll
+        for (int j = 0; j < WS_CB; ++j) {
+          const int n = (c * WS_CB + j) * 32 + l32;
+          const float bv = (bias && n < C) ? bias[n] : 0.0f;
+          auto fin = [&](float v) {
+            if (epi) {
+              v = v + bv;
+              if (relu) v = v > 0.0f ? v : 0.0f;
+            }
+            return v;
+          };
+#if GRL_WS_OUT16_PACK
+          const int odd = lane & 1;
+          const int64_t mr = m0 + 4 * h + odd;  // this lane's row of register pair 0
+          uint16_t* const o = out + mr * ldo + (n - odd);
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int p = 0; p < 8; ++p) {
+              const float v0 = fin(acc[i][j][2 * p]), v1 = fin(acc[i][j][2 * p + 1]);
+              const float got = swap_lane_pair(odd ? v0 : v1);  // the neighbour column's value of this lane's row
+              const uint32_t pk = odd ? cvt_pk_bf16(got, v1) : cvt_pk_bf16(v0, got);
+              const int row = i * 32 + ((2 * p) & 3) + 8 * (p >> 1);
+              if (n < C && (WHOLE || mr + row < M)) *reinterpret_cast<uint32_t*>(o + (int64_t)row * ldo) = pk;
+              acc[i][j][2 * p] = 0.0f;
+              acc[i][j][2 * p + 1] = 0.0f;
+            }
+#else
+          const int64_t mr = m0 + 4 * h;
+          uint16_t* const o = out + mr * ldo + n;
+#pragma unroll
+          for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+              const int row = i * 32 + (r & 3) + 8 * (r >> 2);
+              if (n < C && (WHOLE || mr + row < M))
+                o[(int64_t)row * ldo] = (uint16_t)cvt_pk_bf16(fin(acc[i][j][r]), 0.0f);
+              acc[i][j][r] = 0.0f;
+            }
+#endif
+        }
+      };
+      if (m0 + WS_R <= M)  // wave-uniform
+        store_tile(std::true_type{});
+      else
+        store_tile(std::false_type{});
+#else
       if (m0 + WS_R <= M) {  // whole tile (wave-uniform): row offsets are uniform multiples of C
 #pragma unroll
         for (int j = 0; j < WS_CB; ++j) {
@@ -472,6 +532,7 @@
             acc[i][j][r] = 0.0f;
           }
       }
+#endif
     }
     stamp_out();
   }

@@ -182,6 +182,20 @@ BAG_LINEAR_MAX_C = 512
 
 
 class GraphCNNDropEdge(BaseNetwork):
+    """`activation_dtype` (an attribute set after construction, like
+    `sparse_emb1`; default None): torch.bfloat16 keeps the three GraphConv
+    layers' activations in ONE bfloat16 table [N, 2 net_size] at inference.
+    The embedding is cast once; gcn1 writes the table's columns [0, C), gcn2
+    gathers from that slice and writes [C, 2C), gcn3 gathers from the whole
+    table (no torch.cat, no cast pass: each layer's kernel rounds its fp32
+    result once as it stores it) and returns bfloat16; emb2 takes
+    cat[g1, g3].float(), and everything after it is fp32 as ever.  It applies
+    in eval mode with gradients disabled (torch.no_grad) on an unsharded
+    TypedGraph on the GPU.  In every other situation -- training mode
+    (feature dropout and the gradient kernels are fp32), gradients enabled, a
+    node-range shard, a dense A, the CPU, the default None -- the attribute is
+    ignored and the fp32 path runs, bit for bit as without it."""
+
     def __init__(self, input_dim: int, output_dim: int, num_edges: int, net_size: int = 256,
                  use_attention: bool = True, dropedge_seed: Optional[int] = None):
         super().__init__()
@@ -191,6 +205,8 @@ class GraphCNNDropEdge(BaseNetwork):
         # emb1's input is a bag-of-characters row (~7 nonzeros of 4369): run it
         # as a sparse-row gather (grl_bag_linear_fwd); False = dense torch Linear
         self.sparse_emb1 = True
+        # torch.bfloat16: the GraphConv activations of an eval forward in one bf16 table (class docstring)
+        self.activation_dtype: Optional[torch.dtype] = None
         self.dropout = FeatureDropout(p=0.5, seed=dropedge_seed)
         self.edge_dropout = EdgeDropout(p=0.3, seed=dropedge_seed)
         self.gcn1 = GraphConv(self.net_size, self.net_size, num_edges)
@@ -236,6 +252,9 @@ class GraphCNNDropEdge(BaseNetwork):
         # row-local layers of a shard take the one-GPU model's GEMM path (bitwise its rows)
         pr = graph.global_rows if sharded else 0
         self.dropout.begin_forward(V.device, graph if sharded else None, V.numel() // max(V.shape[-1], 1))
+        if (self.activation_dtype == torch.bfloat16 and not self.training and not torch.is_grad_enabled()
+                and isinstance(A, TypedGraph) and V.is_cuda):
+            return self._head(self._gcn_bf16(V, graph, bool(efficient_mode)), graph, False, pr)
         embedding = self.dropout(self._embed(V))
         # efficient_mode=True: dropout covers the identity block of A_pre
         # (:69,:76); False: dropout hits raw A, identity added after (:72-74).
@@ -256,7 +275,25 @@ class GraphCNNDropEdge(BaseNetwork):
                                  relu=True, dropout=self.dropout)
         if sharded:
             graph.clear_halo_memo()
-        new_v = apply_linear(self.emb2, torch.cat([g1, g3], dim=-1), path_rows=pr)
+        return self._head(torch.cat([g1, g3], dim=-1), graph, sharded, pr)
+
+    def _gcn_bf16(self, V: torch.Tensor, graph: TypedGraph, ds: bool) -> torch.Tensor:
+        """emb1 and the three GraphConv layers of an eval forward with their
+        activations in one bfloat16 table (activation_dtype): emb2's fp32
+        input cat[g1, g3]."""
+        C = self.net_size
+        emb = self._embed(V)  # (eval: the feature dropouts are the identity)
+        lead = emb.shape[:-1]
+        x0 = emb.reshape(-1, C).to(torch.bfloat16)  # the one cast: the first layer's table
+        table = torch.empty(x0.shape[0], 2 * C, dtype=torch.bfloat16, device=x0.device)
+        g1 = self.gcn1.propagate(x0, self.edge_dropout(graph, ds), relu=True, out=table[:, :C])
+        self.gcn2.propagate(g1, self.edge_dropout(graph, ds), relu=True, out=table[:, C:])
+        g3 = self.gcn3.propagate(table, self.edge_dropout(graph, ds), relu=True, out_dtype=torch.bfloat16)
+        return torch.cat([g1, g3], dim=-1).float().view(*lead, 2 * C)
+
+    def _head(self, x: torch.Tensor, graph, sharded: bool, pr: int) -> torch.Tensor:
+        """emb2 -> attention -> random projection -> classifier over x = cat[g1, g3]."""
+        new_v = apply_linear(self.emb2, x, path_rows=pr)
         if self.use_attention:
             new_v = self.self_atten(new_v, shard=graph) if sharded else self.self_atten(new_v)
         new_v = self.dropout(apply_linear(self.w_rand.projection, new_v, relu=True, path_rows=pr))

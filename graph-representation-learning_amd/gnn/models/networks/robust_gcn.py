@@ -19,7 +19,7 @@ from torch import nn
 
 from grl import TypedGraph
 from grl.dist import ShardedGraph, sharded_node_attention
-from grl.ops import graph_conv, node_self_attention, row_linear
+from grl.ops import graph_conv, graph_conv_infer, node_self_attention, row_linear
 
 
 def make_linear_relu(input_dim: int, output_dim: int) -> nn.Sequential:
@@ -108,7 +108,8 @@ class GraphConv(nn.Module):
         return TypedGraph.from_dense(self._on_device(A), layout="pre")
 
     # ------------------------------------------------------------- forward
-    def propagate(self, V: torch.Tensor, graph, relu: bool = False, dropout=None) -> torch.Tensor:
+    def propagate(self, V: torch.Tensor, graph, relu: bool = False, dropout=None, out: torch.Tensor = None,
+                  out_dtype=None) -> torch.Tensor:
         """Aggregate + linear (+ fused ReLU) on a ready TypedGraph, or on this
         rank's node-range shard of a graph (grl.dist.ShardedGraph: V holds the
         shard's rows; the halo exchange runs inside, the output rows are the
@@ -116,8 +117,18 @@ class GraphConv(nn.Module):
         dropout: the feature dropout the model applies to the layer's output
         (drop_robust_gcn.py:77,81,86); on a shard in training it is fused into
         the layer, whose output rows then stream to the peers as they are
-        written."""
+        written.
+        out (inference on a TypedGraph only, no autograd): the [rows, C] tensor
+        the layer writes and returns -- with a bfloat16 V a bfloat16 one of any
+        row stride, e.g. a column slice of the next layer's table
+        (grl.ops.graph_conv_infer).  out_dtype: grl.ops.graph_conv's (a
+        bfloat16 output in a new tensor from a bfloat16 V)."""
         lead = V.shape[:-1]
+        if out is not None:
+            if isinstance(graph, ShardedGraph) or torch.is_grad_enabled():
+                raise ValueError("GraphConv.propagate(out=...) is the inference form on a TypedGraph (torch.no_grad)")
+            res = graph_conv_infer(V, graph, self.h_weights, self.bias, relu, out=out)
+            return dropout(res) if dropout is not None else res
         if isinstance(graph, ShardedGraph):
             V2 = V.reshape(-1, V.shape[-1])
             training = torch.is_grad_enabled() and any(t is not None and t.requires_grad
@@ -130,7 +141,8 @@ class GraphConv(nn.Module):
                 out = dropout(out) if dropout is not None else out
             return out.view(*lead, self.C)
         # new_V = A_pre V (B*N, (L+1)F) then new_V h_weights + bias, one autograd node
-        out = graph_conv(V, graph, self.h_weights, self.bias, relu=relu, recompute=self.recompute_aggregation)
+        out = graph_conv(V, graph, self.h_weights, self.bias, relu=relu, recompute=self.recompute_aggregation,
+                         out_dtype=out_dtype)
         out = out.view(*lead, self.C)
         return dropout(out) if dropout is not None else out
 

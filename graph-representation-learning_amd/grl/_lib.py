@@ -160,6 +160,13 @@ SIGNATURES = {
                                         _P(GrlDropEdge), _c_vp, _c_size, _c_vp]),
     "grl_graphconv_fwd_train_bf16": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i32, _c_i32,
                                               _c_vp, _c_vp, _P(GrlDropEdge), _c_vp, _c_size, _c_vp]),
+    "grl_graphconv_fwd_bf16_to_bf16_workspace_query": (_c_size, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_i32,
+                                                                 _c_vp, _c_i64]),
+    "grl_graphconv_fwd_bf16_to_bf16": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i32, _c_i32,
+                                                _c_vp, _c_i64, _P(GrlDropEdge), _c_vp, _c_size, _c_vp]),
+    "grl_graphconv_fwd_train_bf16_to_bf16": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i32,
+                                                      _c_i32, _c_vp, _c_i64, _c_vp, _P(GrlDropEdge), _c_vp, _c_size,
+                                                      _c_vp]),
     "grl_linear_fwd_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32]),
     "grl_linear_fwd": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_vp, _c_size,
                                 _c_vp]),

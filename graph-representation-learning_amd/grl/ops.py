@@ -49,9 +49,12 @@ def _de_ref(graph):
 _TABLE_DTYPES = (torch.float32, torch.bfloat16)
 
 
-def _bf16_suffix(X2: torch.Tensor) -> str:
-    """'_bf16' for a bfloat16 table: the grl_graphconv_fwd*_bf16 entries."""
-    return "_bf16" if X2.dtype == torch.bfloat16 else ""
+def _bf16_suffix(X2: torch.Tensor, out: torch.Tensor = None) -> str:
+    """'_bf16' for a bfloat16 table: the grl_graphconv_fwd*_bf16 entries;
+    '_bf16_to_bf16' when `out` is bfloat16 too."""
+    if X2.dtype != torch.bfloat16:
+        return ""
+    return "_bf16_to_bf16" if out is not None and out.dtype == torch.bfloat16 else "_bf16"
 
 
 def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: bool = False):
@@ -60,7 +63,9 @@ def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: 
     [segments * F, C] and bias (None without), out [num_rows, C] (with
     weights) and Z [num_rows, segments * F] (want_Z), each the contiguous
     fp32 tensor given or a new one.  The features may be bfloat16 (the table
-    is read as stored); weights and bias are float32."""
+    is read as stored); weights and bias are float32.  With bfloat16 features
+    `out` may be a bfloat16 [num_rows, C] tensor with unit column stride and
+    any row stride (a column-slice view of a wider table), written in place."""
     _require_device(X, "node features")
     if X.dtype not in _TABLE_DTYPES:
         raise _lib.GrlError(f"{who}: node features must be float32 or bfloat16 (got {X.dtype})")
@@ -79,6 +84,14 @@ def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: 
         shape = (graph.num_rows, cols)
         if t is None:
             return torch.empty(shape, dtype=torch.float32, device=X.device)
+        if what == "out" and t.dtype == torch.bfloat16:
+            if X.dtype != torch.bfloat16:
+                raise _lib.GrlError(f"{who}: a bfloat16 out needs bfloat16 node features (got {X.dtype}): there is no "
+                                    "fp32-table form with a bf16 output -- cast the table once")
+            if tuple(t.shape) != shape or t.stride(1) != 1 or t.stride(0) < cols or t.device != X.device:
+                raise _lib.GrlError(f"{who}: a bfloat16 out must be a {shape} tensor on {X.device} with unit column "
+                                    "stride and a row stride of at least its width")
+            return t
         if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != X.device:
             raise _lib.GrlError(f"{who}: {what} must be a contiguous float32 {shape} tensor on {X.device}")
         return t
@@ -495,17 +508,20 @@ class _GraphConv(torch.autograd.Function):
     39-41 ms per C3 layer either way, each kernel already fills the chip.)"""
 
     @staticmethod
-    def forward(ctx, X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b, relu: bool, recompute: bool):
+    def forward(ctx, X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b, relu: bool, recompute: bool,
+                out_bf16: bool = False):
         Wc = W.contiguous()
         bc = b.contiguous() if b is not None else None
+        # out_bf16 (a bf16 X on a TypedGraph: graph_conv checks): the layer's epilogue writes bf16
+        out = torch.empty(graph.num_rows, Wc.shape[1], dtype=torch.bfloat16, device=X.device) if out_bf16 else None
         if isinstance(graph, EdgeBlockedGraph):
             Z = spmm_forward(X, graph)
             out = linear_fwd(Z, Wc, bc, relu)
         elif recompute:  # Z is not kept: the one-kernel inference form (Z stays on chip)
             Z = None
-            out = graph_conv_infer(X, graph, Wc, bc, relu)
+            out = graph_conv_infer(X, graph, Wc, bc, relu, out=out)
         else:  # one kernel that also writes Z where it applies (grl_graphconv_fwd_train)
-            out, Z = graph_conv_fwd_train(X, graph, Wc, bc, relu)
+            out, Z = graph_conv_fwd_train(X, graph, Wc, bc, relu, out=out)
         ctx.graph, ctx.relu, ctx.has_b, ctx.xshape, ctx.xdtype = graph, relu, b is not None, X.shape, X.dtype
         ctx.recompute = recompute
         # recompute: keep X (F wide) instead of Z ((L+1)F wide); the backward
@@ -518,7 +534,9 @@ class _GraphConv(torch.autograd.Function):
         Z, W, out = ctx.saved_tensors
         want_w = ctx.needs_input_grad[2]
         want_b = ctx.has_b and ctx.needs_input_grad[3]
-        g, mask, db_pre = relu_grad(g.contiguous().float(), out if ctx.relu else None, want_b)
+        # a bf16 out hands back a bf16 g: the fp32 layer's backward on g.float(), the ReLU mask from the bf16
+        # out ([out > 0] survives the rounding); both widened to fp32 here
+        g, mask, db_pre = relu_grad(g.contiguous().float(), out.float() if ctx.relu else None, want_b)
         if ctx.recompute and ctx.needs_input_grad[0] and want_w and ctx.xdtype == torch.float32:
             # X was kept, not Z: the one-kernel data gradient also writes G_s = A_drop,s^T g and
             # dW_s = Z_s^T g = X^T G_s -- no re-aggregation of Z (same products, another order).
@@ -532,7 +550,7 @@ class _GraphConv(torch.autograd.Function):
                 del G_agg
                 dW = dWt.view(F, S, C).transpose(0, 1).reshape(S * F, C)
                 db = (db_pre if db_pre is not None else g_eff.sum(0)) if want_b else None
-                return dX.view(ctx.xshape), None, dW, db, None, None
+                return dX.view(ctx.xshape), None, dW, db, None, None, None
         if ctx.recompute and (want_w or (want_b and db_pre is None)):
             Z = spmm_forward(Z, ctx.graph)
         dW = db = dX = None
@@ -548,7 +566,7 @@ class _GraphConv(torch.autograd.Function):
             dW, db = linear_bwd_weight(Z, g, mask, want_b and db_pre is None)
         if db_pre is not None:
             db = db_pre
-        return dX, None, dW if want_w else None, db, None, None
+        return dX, None, dW if want_w else None, db, None, None, None
 
 
 def graph_conv_fwd_train(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu: bool = False,
@@ -558,13 +576,24 @@ def graph_conv_fwd_train(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=
     result is bitwise spmm_forward then linear_fwd.  out / Z: contiguous
     [num_rows, C] / [num_rows, segments * F] fp32 tensors to write (e.g. the
     row block of a streamed layer).  X float32, or bfloat16 read as stored
-    (grl_graphconv_fwd_train_bf16): out and Z bitwise the call's on X.float()."""
+    (grl_graphconv_fwd_train_bf16): out and Z bitwise the call's on X.float().
+    With a bfloat16 X, out may be bfloat16 (_forward_args; a column-slice view
+    is written in place, grl_graphconv_fwd_train_bf16_to_bf16): the fp32 out
+    rounded to nearest even in the kernel's epilogue, Z fp32 as before."""
     X2, F, Wc, bc, out, Z = _forward_args("graph_conv_fwd_train", X, graph, W, b, out, Z, want_Z=True)
     K, C = Wc.shape
+    csr = graph.csr_c(F)
     ws_bytes = _lib.lib().grl_linear_fwd_ex_workspace_size(graph.num_rows, K, C, graph.path_rows)
+    sfx = _bf16_suffix(X2, out)
+    args = [ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc), C, int(relu), out.data_ptr()]
+    if out.dtype == torch.bfloat16:
+        args.append(out.stride(0))
+        full = _lib.lib().grl_graphconv_fwd_bf16_to_bf16_workspace_query(
+            ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), C, out.data_ptr(), out.stride(0))
+        if full >= graph.num_rows * K * 4 or Z.data_ptr() % 16:  # two kernels: the linear's fp32 [num_rows, C]
+            ws_bytes += (graph.num_rows * C * 4 + 255) // 256 * 256
     ws = _workspace(ws_bytes, X.device)
-    call("grl_graphconv_fwd_train" + _bf16_suffix(X2), ctypes.byref(graph.csr_c(F)), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(),
-         _ptr(bc), C, int(relu), out.data_ptr(), Z.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes,
+    call("grl_graphconv_fwd_train" + sfx, *args, Z.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes,
          current_stream_handle(X.device))
     return out, Z
 
@@ -580,18 +609,24 @@ def graph_conv_infer(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None
     X float32, or bfloat16 read as stored (grl_graphconv_fwd_bf16: out bitwise
     the call's on X.float(); one kernel where X is 8 B-aligned with a row
     stride that is a multiple of 4, else Z whole in the workspace -- the bf16
-    entry has no row-chunked form, so a max_workspace_bytes below that raises)."""
+    entry has no row-chunked form, so a max_workspace_bytes below that raises).
+    With a bfloat16 X, out may be bfloat16 with any row stride, e.g. a column
+    slice of the next layer's table (grl_graphconv_fwd_bf16_to_bf16): bitwise
+    the fp32 out rounded to nearest even, written by the kernel's epilogue --
+    one kernel where, besides, out is 4 B-aligned with an even row stride."""
     X2, F, Wc, bc, out, _ = _forward_args("graph_conv_infer", X, graph, W, b, out)
     C = Wc.shape[1]
     csr = graph.csr_c(F)
-    sfx = _bf16_suffix(X2)
-    # the fused one-kernel path needs only W's planes; else Z whole
+    sfx = _bf16_suffix(X2, out)
+    out16 = out.dtype == torch.bfloat16
+    out_args = [out.data_ptr(), out.stride(0)] if out16 else [out.data_ptr()]
+    # the fused one-kernel path needs only W's planes; else Z whole (the bf16-out rule also looks at out's rows)
     query = getattr(_lib.lib(), f"grl_graphconv_fwd{sfx}_workspace_query")
-    full = query(ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), C)
+    full = query(ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), C, *(out_args if out16 else []))
     ws_bytes = full if max_workspace_bytes is None else min(full, int(max_workspace_bytes))
     ws = _workspace(ws_bytes, X.device)
     call("grl_graphconv_fwd" + sfx, ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc), C,
-         int(relu), out.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes, current_stream_handle(X.device))
+         int(relu), *out_args, _de_ref(graph), _ptr(ws), ws_bytes, current_stream_handle(X.device))
     return out
 
 
@@ -604,7 +639,7 @@ RECOMPUTE_Z_BYTES = 8 << 30
 
 
 def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu: bool = False,
-               recompute: bool = None) -> torch.Tensor:
+               recompute: bool = None, out_dtype=None) -> torch.Tensor:
     """GraphConv forward (aggregation + linear [+ReLU]) as one autograd node;
     X: [num_cols, F] (or [B, N, F] for a batch graph).  When no gradient is
     wanted (eval, torch.no_grad) it is one grl_graphconv_fwd call instead:
@@ -627,19 +662,34 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
     its dX rounded once to bfloat16.  With recompute=True the bf16 X is what
     is kept, and the backward re-aggregates Z from it (the bf16 SpMM, the
     same bits): it does not take the dW_s = X^T G_s form, which needs an
-    fp32 X, so dW and db stay bitwise the saved-Z path's."""
+    fp32 X, so dW and db stay bitwise the saved-Z path's.
+    out_dtype=torch.bfloat16 (a bfloat16 X on a TypedGraph only; None and
+    torch.float32: the fp32 output as ever): a new contiguous bfloat16 tensor
+    written by the kernel's epilogue (grl_graphconv_fwd[_train]_bf16_to_bf16),
+    bitwise the fp32 output rounded to nearest even, from the same one
+    autograd node.  Autograd then hands the node a bfloat16 output gradient;
+    the backward is the fp32 layer's on g.float() with the ReLU mask taken
+    from the bfloat16 output, dX rounded once as above.  recompute=True keeps
+    the bf16 X and re-aggregates Z, as above."""
     if X.dtype not in _TABLE_DTYPES:
         raise _lib.GrlError(f"graph_conv: node features must be float32 or bfloat16 (got {X.dtype})")
     if W.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
         raise _lib.GrlError("graph_conv: weights and bias must be float32")
+    if out_dtype not in (None, torch.float32, torch.bfloat16):
+        raise _lib.GrlError(f"graph_conv: out_dtype must be None, float32 or bfloat16 (got {out_dtype})")
+    out_bf16 = out_dtype == torch.bfloat16
+    if out_bf16 and (X.dtype != torch.bfloat16 or isinstance(graph, EdgeBlockedGraph)):
+        raise _lib.GrlError(f"graph_conv: out_dtype=bfloat16 needs bfloat16 node features on a TypedGraph (got "
+                            f"{X.dtype}): there is no fp32-table form with a bf16 output -- cast the table once")
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (X, W, b))):
         if isinstance(graph, EdgeBlockedGraph):  # one int32 CSR per call: aggregate by blocks, then the linear
             return linear_fwd(spmm_forward(X, graph), W.contiguous(), b.contiguous() if b is not None else None,
                               relu)
-        return graph_conv_infer(X, graph, W, b, relu)
+        out = torch.empty(graph.num_rows, W.shape[1], dtype=torch.bfloat16, device=X.device) if out_bf16 else None
+        return graph_conv_infer(X, graph, W, b, relu, out=out)
     if recompute is None:
         recompute = graph.num_rows * graph.segments * X.shape[-1] * 4 > RECOMPUTE_Z_BYTES
-    return _GraphConv.apply(X, graph, W, b, relu, bool(recompute))
+    return _GraphConv.apply(X, graph, W, b, relu, bool(recompute), out_bf16)
 
 
 def graph_linear(Z: torch.Tensor, W: torch.Tensor, b=None, relu: bool = False, path_rows: int = 0) -> torch.Tensor:

@@ -440,6 +440,48 @@ int grl_graphconv_fwd_train_bf16(const GrlTypedCsr* g, const uint16_t* X,
                                  void* workspace, size_t workspace_bytes,
                                  grl_stream_t stream);
 
+/* The bf16-table entries above writing a bf16 table: out holds bf16 bits,
+ * row n at out + n * ldo (ldo >= C, counted in bf16 elements), so a layer
+ * can fill a column range of a wider table and the next layer gather from
+ * it, with no cast pass and no concatenation in between.
+ *   out is BITWISE the round-to-nearest-even bf16 of what the matching _bf16
+ *   entry writes (bias, then ReLU, in fp32; rounded once); Z (training
+ *   entry) stays fp32 with row stride K and is bitwise that entry's.
+ * X and out may be disjoint column ranges of one allocation (gcn2 reads
+ * table[:, 0:C] and writes table[:, C:2C]); ranges that overlap are
+ * undefined.  Columns of a row outside [0, C) are never written.
+ * One kernel (the persistent form; its MFMA waves round the finished tile in
+ * registers and store two columns per dword) where the _bf16 entries' rule
+ * holds AND out is 4 B-aligned with ldo even; the workspace query then
+ * answers the size of W's planes.  Elsewhere grl_typed_spmm_fwd_bf16 into Z,
+ * grl_linear_fwd_ex with g->path_rows into an fp32 [num_rows, C] scratch in
+ * the workspace, and a rounding pass into out -- the same bits.  The
+ * inference entry then needs the query's size (Z whole, the scratch, the
+ * linear's workspace); the training entry, whose Z is the caller's, needs
+ * roundup(num_rows * C * 4, 256) + grl_linear_fwd_ex_workspace_size(num_rows,
+ * K, C, g->path_rows).  A smaller workspace: GRL_E_WORKSPACE.
+ * GRL_E_INVALID, decided on the host: the _bf16 entries' checks, NULL out,
+ * ldo < C, X or out not 2 B-aligned (the query answers 0 for ldo < C).
+ * There is no fp32-table form and no data-gradient form with a bf16 output:
+ * a model's first table is cast once by the caller.  A bounded wait that runs
+ * out fills out's C columns of every row (and Z) with NaN and is reported by
+ * grl_check() under these entries' names.                                  */
+size_t grl_graphconv_fwd_bf16_to_bf16_workspace_query(
+    const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+    const float* W, int32_t C, const uint16_t* out, int64_t ldo);
+int grl_graphconv_fwd_bf16_to_bf16(const GrlTypedCsr* g, const uint16_t* X,
+                                   int64_t ldx, int32_t F, const float* W,
+                                   const float* bias, int32_t C, int32_t relu,
+                                   uint16_t* out, int64_t ldo,
+                                   const GrlDropEdge* de, void* workspace,
+                                   size_t workspace_bytes,
+                                   grl_stream_t stream);
+int grl_graphconv_fwd_train_bf16_to_bf16(
+    const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+    const float* W, const float* bias, int32_t C, int32_t relu, uint16_t* out,
+    int64_t ldo, float* Z, const GrlDropEdge* de, void* workspace,
+    size_t workspace_bytes, grl_stream_t stream);
+
 /* Data gradient of one GraphConv layer in ONE kernel.  Replaces the
  * autograd chain MmBackward0 (dZ = G W^T, robust_gcn.py:50) then
  * BmmBackward0 (dX = A_drop^T dZ, robust_gcn.py:45) by its reassociation
