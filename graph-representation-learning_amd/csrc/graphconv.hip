@@ -19,7 +19,10 @@
 //  * graphconv_ws_bf16o_kernel: graphconv_ws_bf16_kernel writing bf16 rows
 //    with a caller-given stride (grl_graphconv_fwd_bf16_to_bf16,
 //    _fwd_train_bf16_to_bf16): the epilogue rounds the finished tile to
-//    nearest even in registers and stores two columns per dword.
+//    nearest even in registers and stores two columns per dword;
+//  * graphconv_ws_bf16g_kernel: the data-gradient form of that kernel
+//    (grl_graphconv_bwd_data_bf16): it gathers a bf16 gradient table over the
+//    typed transpose and writes bf16 dX rows.
 // Shared pieces: the gather sums a wave's rows' segment-t neighbour rows
 // (one float4 per lane, one 1 KB row per wave-instruction, the rows' edge
 // lists streamed as one list with flushes at row boundaries); the multiply
@@ -576,6 +579,28 @@ __global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_bf16o_kernel(
 #undef GRL_WS_BF16
 }
 
+// The data-gradient form over a bf16 gradient table, writing bf16 rows
+// (grl_graphconv_bwd_data_bf16): graphconv_ws_kernel's EID form -- entry e's
+// DropEdge id through eid, the self term for rows < self_rows -- with
+// graphconv_ws_bf16o_kernel's gather loads (X = G, bf16 bits, ldx apart a
+// row) and epilogue (out = dX, bf16 bits, ldo apart a row).  Zout (G_agg)
+// stays fp32.  The same body text: no line of it is this kernel's alone.
+template <int KS, bool VALS, int FV = 1, int PROD = 8>
+__global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_bf16g_kernel(
+    int64_t M, int L, int hs, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+    const float* __restrict__ vals, uint64_t edge_base, uint64_t self_base, const uint16_t* __restrict__ X,
+    int64_t ldx, const uint16_t* __restrict__ Wf, const float* __restrict__ bias, int relu,
+    uint16_t* __restrict__ out, int C, DropDev de, int64_t num_tiles, float* __restrict__ Zout, int64_t ldz,
+    const int32_t* __restrict__ eid, int64_t self_rows, int spin_limit, int* __restrict__ status,
+    int64_t self_row0, int64_t ldo) {
+  constexpr bool EID = true;
+#define GRL_WS_BF16 1
+#define GRL_WS_OUT16 1
+#include "graphconv_ws_body.inc"
+#undef GRL_WS_OUT16
+#undef GRL_WS_BF16
+}
+
 }  // namespace
 
 #if GRL_WS_STAMP
@@ -623,8 +648,9 @@ static int ws_spin_limit() {
 __device__ int g_grl_sticky;  // WS_WHO_* bits of the calls whose outputs were poisoned
 
 constexpr int WS_WHO_FWD = 1, WS_WHO_FWD_TRAIN = 2, WS_WHO_BWD_DATA = 4, WS_WHO_FWD_BF16 = 8,
-              WS_WHO_FWD_TRAIN_BF16 = 16, WS_WHO_FWD_BF16_TO_BF16 = 32, WS_WHO_FWD_TRAIN_BF16_TO_BF16 = 64;
-constexpr int WS_WHO_COUNT = 7;
+              WS_WHO_FWD_TRAIN_BF16 = 16, WS_WHO_FWD_BF16_TO_BF16 = 32, WS_WHO_FWD_TRAIN_BF16_TO_BF16 = 64,
+              WS_WHO_BWD_DATA_BF16 = 128;
+constexpr int WS_WHO_COUNT = 8;
 
 __global__ void ws_poison_kernel(const int* __restrict__ status, float* __restrict__ a, int64_t na,
                                  float* __restrict__ b, int64_t nb, int who) {
@@ -658,6 +684,7 @@ static const char* who_name(int who) {
          : who == WS_WHO_FWD_BF16          ? "grl_graphconv_fwd_bf16"
          : who == WS_WHO_FWD_TRAIN_BF16    ? "grl_graphconv_fwd_train_bf16"
          : who == WS_WHO_FWD_BF16_TO_BF16  ? "grl_graphconv_fwd_bf16_to_bf16"
+         : who == WS_WHO_BWD_DATA_BF16     ? "grl_graphconv_bwd_data_bf16"
                                            : "grl_graphconv_fwd_train_bf16_to_bf16";
 }
 
@@ -687,11 +714,12 @@ static int graphconv_status(const int* status, OT* a, int64_t M, int C, int64_t 
 
 // One launch of the persistent kernel for gathered width F and output width
 // C over a table of XT (float, or uint16_t: bf16 bits): the template instance
-// for (F, C > 256) with or without edge values / eid (the data-gradient form,
-// fp32 only); grid = one workgroup per CU (at most the tiles).  The bf16
-// kernels have no eid / self_rows arguments.  OT = uint16_t: out holds bf16
-// bits with row stride ldo (graphconv_ws_bf16o_kernel; the forward over a bf16
-// table only); OT = float: out is [M, C] contiguous and ldo is not looked at.
+// for (F, C > 256) with or without edge values / eid (the data-gradient form:
+// fp32 table and out, or bf16 table and out -- graphconv_ws_bf16g_kernel);
+// grid = one workgroup per CU (at most the tiles).  The bf16 forward kernels
+// have no eid / self_rows arguments.  OT = uint16_t (a bf16 table only): out
+// holds bf16 bits with row stride ldo (graphconv_ws_bf16o_kernel, _bf16g_);
+// OT = float: out is [M, C] contiguous and ldo is not looked at.
 template <typename XT, bool EID, typename OT = float>
 static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M, int L, int hs,
                       const GrlTypedCsr* g, const XT* X, int64_t ldx, const uint16_t* Wf, const float* bias,
@@ -699,14 +727,17 @@ static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M
                       const int32_t* eid, int64_t self_rows, int spin, int* status) {
   constexpr bool BF16 = std::is_same<XT, uint16_t>::value;
   constexpr bool OUT16 = std::is_same<OT, uint16_t>::value;
-  static_assert(!(BF16 && EID), "no data-gradient form over a bf16 table");
-  static_assert(!OUT16 || (BF16 && !EID), "bf16 output: the forward over a bf16 table only");
+  static_assert(!(BF16 && EID) || OUT16, "the data-gradient form over a bf16 table writes a bf16 dX only");
+  static_assert(!OUT16 || BF16, "bf16 output: over a bf16 table only");
 #define GRL_WS_HEAD                                                                                                \
   grid, dim3(64 * WS_WAVES), 0, st, M, L, hs, g->rowptr, g->colidx, g->vals, g->edge_id_base, g->self_id_base, X, \
       ldx, Wf, bias, relu, out, C, d, tiles, Z, ldz
 #define GRL_WS_INST(KS_, VALS_, FV_, PROD_)                                                                       \
   do {                                                                                                            \
-    if constexpr (OUT16)                                                                                          \
+    if constexpr (OUT16 && EID)                                                                                   \
+      hipLaunchKernelGGL((graphconv_ws_bf16g_kernel<KS_, VALS_, FV_, PROD_>), GRL_WS_HEAD, eid, self_rows, spin,  \
+                         status, g->self_row0, ldo);                                                              \
+    else if constexpr (OUT16)                                                                                     \
       hipLaunchKernelGGL((graphconv_ws_bf16o_kernel<KS_, VALS_, FV_, PROD_>), GRL_WS_HEAD, spin, status,          \
                          g->self_row0, ldo);                                                                      \
     else if constexpr (BF16)                                                                                      \
@@ -813,10 +844,13 @@ static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, i
 // dX = sum_s G_s W_s^T over the typed transpose gt (grl_graphconv_bwd_data):
 // graphconv_ws_kernel with the rows' CSC segments, DropEdge ids through eid,
 // and W's planes taken block-transposed.  Cin = G's width (the forward's C),
-// Cout = dX's width (the forward's F).
-static int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const float* G, int64_t ldg,
-                                    int64_t self_rows, int Cin, const float* W, int Cout, float* dX, float* Gagg,
-                                    const GrlDropEdge* de, void* ws, hipStream_t st) {
+// Cout = dX's width (the forward's F).  GT = OT = float: G fp32, dX [M, Cout]
+// contiguous (lddx = Cout); GT = OT = uint16_t: both hold bf16 bits, dX's rows
+// lddx apart (grl_graphconv_bwd_data_bf16, graphconv_ws_bf16g_kernel).
+template <typename GT, typename OT>
+static int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const GT* G, int64_t ldg,
+                                    int64_t self_rows, int Cin, const float* W, int Cout, OT* dX, int64_t lddx,
+                                    float* Gagg, const GrlDropEdge* de, void* ws, hipStream_t st) {
   const int hs = gt->has_self ? 1 : 0;
   const int64_t K = (int64_t)segments(gt) * Cin;
   uint16_t* Wf = static_cast<uint16_t*>(ws);
@@ -827,17 +861,19 @@ static int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, c
   GRL_LAUNCH_CHECK();
   const int64_t M = gt->num_rows;
   const int64_t ws_tiles = ceil_div(M, WS_R);
-  GRL_CHECK_ARG(ws_tiles < 2147483647LL, "grl_graphconv_bwd_data: too many row tiles");
+  GRL_CHECK_ARG(ws_tiles < 2147483647LL, "%s: too many row tiles",
+                who_name(std::is_same<OT, uint16_t>::value ? WS_WHO_BWD_DATA_BF16 : WS_WHO_BWD_DATA));
   const int64_t grid = std::min<int64_t>(ws_tiles, (int64_t)device_cu_count());
   const DropDev d = to_dev(de);
   const bool v = gt->vals != nullptr;
   int* status = ws_status(ws, K, Cout);
   const int spin = ws_spin_limit();
   GRL_HIP(hipMemsetAsync(status, 0, sizeof(int), st));
-  launch_ws<float, true>(Cin, Cout, v, dim3((unsigned)grid), st, M, gt->num_types, hs, gt, G, ldg, Wf, nullptr, 0, dX,
-                         (int64_t)Cout, d, ws_tiles, Gagg, K, eid, self_rows, spin, status);
+  launch_ws<GT, true, OT>(Cin, Cout, v, dim3((unsigned)grid), st, M, gt->num_types, hs, gt, G, ldg, Wf, nullptr, 0, dX,
+                          lddx, d, ws_tiles, Gagg, K, eid, self_rows, spin, status);
   GRL_LAUNCH_CHECK();
-  return graphconv_status(status, dX, M, Cout, (int64_t)Cout, Gagg, M * K, st, WS_WHO_BWD_DATA);
+  return graphconv_status(status, dX, M, Cout, lddx, Gagg, M * K, st,
+                          std::is_same<OT, uint16_t>::value ? WS_WHO_BWD_DATA_BF16 : WS_WHO_BWD_DATA);
 }
 
 // ---- the layer's dispatch: which kernels a grl_graphconv_* call runs -------
@@ -910,6 +946,19 @@ static int out16_check(const char* who, const void* X, const void* out, int64_t 
 static bool bwd_data_path(const GrlTypedCsr* gt, const float* G, int64_t ldg, int C, const float* W, int F) {
   return grl_graphconv_bwd_data_shape_ok(gt->num_rows, gt->num_types, gt->has_self, C, F) && gt->self_row0 == 0 &&
          al16(W) && al16(G) && ldg % 4 == 0 && ldg < (1LL << 30) && (!gt->split || gt->split->num_heavy == 0) &&
+         gt->nnz < 2147483647LL;
+}
+
+// grl_graphconv_bwd_data_bf16 (G and dX hold bf16 bits): the same rule with
+// the alignments restated -- a G row takes the gather's 8 B load of a lane's 4
+// columns and its bytes fit 32 bits, a dX row the epilogue's dword stores of
+// two columns -- and the graphconv_bwd_bf16 path option on.
+static bool bwd_data_path_bf16(const GrlTypedCsr* gt, const uint16_t* G, int64_t ldg, int C, const float* W, int F,
+                               const uint16_t* dX, int64_t lddx) {
+  return opt(OPT_GRAPHCONV_BWD_BF16) != 0 &&
+         grl_graphconv_bwd_data_shape_ok(gt->num_rows, gt->num_types, gt->has_self, C, F) && gt->self_row0 == 0 &&
+         al16(W) && reinterpret_cast<uintptr_t>(G) % 8 == 0 && ldg % 4 == 0 && ldg < (1LL << 31) &&
+         reinterpret_cast<uintptr_t>(dX) % 4 == 0 && lddx % 2 == 0 && (!gt->split || gt->split->num_heavy == 0) &&
          gt->nnz < 2147483647LL;
 }
 
@@ -1173,7 +1222,45 @@ extern "C" int grl_graphconv_bwd_data(const GrlTypedCsr* gt, const int32_t* eid,
   const size_t need = graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F);
   if (!workspace || !al16(workspace) || workspace_bytes < need)
     GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_bwd_data: workspace %zu < %zu (16-B aligned)", workspace_bytes, need);
-  return graphconv_fused_bwd_data(gt, eid, G, ldg, g_rows, C, W, F, dX, G_agg, de, workspace, as_stream(stream));
+  return graphconv_fused_bwd_data(gt, eid, G, ldg, g_rows, C, W, F, dX, (int64_t)F, G_agg, de, workspace,
+                                  as_stream(stream));
+}
+
+extern "C" size_t grl_graphconv_bwd_data_bf16_workspace_query(const GrlTypedCsr* gt, const uint16_t* G, int64_t ldg,
+                                                             int32_t C, const float* W, int32_t F, const uint16_t* dX,
+                                                             int64_t lddx) {
+  if (!gt || gt->num_rows <= 0 || gt->num_types < 1 || C <= 0 || F <= 0 || !dX || lddx < F || ldg < C) return 0;
+  return bwd_data_path_bf16(gt, G, ldg, C, W, F, dX, lddx) ? graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F) : 0;
+}
+
+extern "C" int grl_graphconv_bwd_data_bf16(const GrlTypedCsr* gt, const int32_t* eid, const uint16_t* G, int64_t ldg,
+                                           int64_t g_rows, int32_t C, const float* W, int32_t F, uint16_t* dX,
+                                           int64_t lddx, float* G_agg, const GrlDropEdge* de, void* workspace,
+                                           size_t workspace_bytes, grl_stream_t stream) {
+  const char* const who = "grl_graphconv_bwd_data_bf16";
+  TraceRange trace_(who);
+  GRL_CHECK_ARG(gt != nullptr, "%s: graph is NULL", who);
+  GRL_CHECK_ARG(gt->num_rows >= 0 && gt->num_types >= 1 && gt->num_types <= 63,
+                "%s: num_types must be in [1, 63] (got %d)", who, gt->num_types);
+  GRL_CHECK_ARG(C > 0 && ldg >= C && F > 0 && g_rows >= 0 && g_rows <= gt->num_rows,
+                "%s: need C > 0, ldg >= C, F > 0, 0 <= g_rows <= num_rows", who);
+  GRL_CHECK_ARG(lddx >= F, "%s: need lddx >= F (lddx=%lld F=%d)", who, (long long)lddx, F);
+  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(G) % 2 == 0 && reinterpret_cast<uintptr_t>(dX) % 2 == 0,
+                "%s: G and dX hold 2-byte elements and must be 2-B aligned", who);
+  if (gt->num_rows == 0) return GRL_OK;
+  // (an empty node-range shard: no G rows and no entries, so its empty G is never read)
+  GRL_CHECK_ARG((G || (g_rows == 0 && gt->nnz == 0)) && W && dX && gt->rowptr && (gt->nnz == 0 || (gt->colidx && eid)),
+                "%s: NULL pointer", who);
+  GRL_CHECK_ARG(al16(G_agg), "%s: G_agg must be 16-B aligned (the gather waves' 16 B row stores)", who);
+  if (!bwd_data_path_bf16(gt, G, ldg, C, W, F, dX, lddx))
+    GRL_FAIL(GRL_E_UNSUPPORTED, "%s: outside the one-kernel path (C %d, F %d, L %d, rows %lld, the operands' "
+             "alignment or the graphconv_bwd_bf16 option; see grl_graphconv_bwd_data_bf16_workspace_query)", who, C, F,
+             gt->num_types, (long long)gt->num_rows);
+  const size_t need = graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F);
+  if (!workspace || !al16(workspace) || workspace_bytes < need)
+    GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu (16-B aligned)", who, workspace_bytes, need);
+  return graphconv_fused_bwd_data(gt, eid, G, ldg, g_rows, C, W, F, dX, lddx, G_agg, de, workspace,
+                                  as_stream(stream));
 }
 
 namespace grl {

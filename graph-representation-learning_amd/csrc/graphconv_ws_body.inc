@@ -3,7 +3,9 @@
 // GRL_WS_BF16 defined: 0 = graphconv_ws_kernel (X fp32), 1 =
 // graphconv_ws_bf16_kernel (X bf16 bits), and GRL_WS_OUT16: 1 (with
 // GRL_WS_BF16 1) = graphconv_ws_bf16o_kernel, whose epilogue alone differs
-// (out holds bf16 bits, ldo apart a row).  Textual sharing, not a function
+// (out holds bf16 bits, ldo apart a row), or -- with EID true and eid /
+// self_rows real arguments -- graphconv_ws_bf16g_kernel, the data-gradient
+// form of that kernel.  Textual sharing, not a function
 // template: the fp32 kernels' machine code is pinned
 // (tests/test_codegen_pin.py); an inlined function template around the body,
 // and a traits class around the loads alone, each moved every one of them,

@@ -164,6 +164,8 @@ int device_cu_count();
   X(OPT_GRAPHCONV_FUSED, "graphconv_fused", 1, 0, 1)                                      \
   /* 1: one-kernel GraphConv data gradient (read by the host layer) */                    \
   X(OPT_GRAPHCONV_FUSED_BWD, "graphconv_fused_bwd", 1, 0, 1)                              \
+  /* 1: grl_graphconv_bwd_data_bf16 eligible (bf16 gradient table, bf16 dX); 0: never */  \
+  X(OPT_GRAPHCONV_BWD_BF16, "graphconv_bwd_bf16", 1, 0, 1)                                \
   /* 1: persistent warp-specialized one-kernel form; 0: phase-alternating */              \
   X(OPT_FG_WS, "fg_ws", 1, 0, 1)                                                          \
   /* -1: whole-row waves for tables > 12 GB; 1 / 0: always / never */                     \

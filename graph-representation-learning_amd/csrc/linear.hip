@@ -424,6 +424,52 @@ __global__ __launch_bounds__(256) void relu_grad_colsum_kernel(const float* g, c
   if (partial) partial[z * C + c] = s;
 }
 
+// relu_grad_colsum_kernel over bf16 bits (grl_relu_grad_bf16): g and relu_out
+// are read once, 2 B a lane, rows ldg / ldo apart; x = relu_out > 0 ? g : +0 is
+// a selection, so nothing is rounded.  Each of the outputs may be NULL: g_eff16
+// (x's bits, rows lde apart; may alias g), g_eff32 (x widened, [M, C]
+// contiguous) and partial (the same row blocks and order as above, so db is
+// bitwise that kernel's on the widened operands).
+__global__ __launch_bounds__(256) void relu_grad_bf16_colsum_kernel(const uint16_t* g, int64_t ldg,
+                                                                     const uint16_t* __restrict__ relu_out, int64_t ldo,
+                                                                     uint16_t* g_eff16, int64_t lde,
+                                                                     float* __restrict__ g_eff32, int64_t M, int64_t C,
+                                                                     int64_t rows_per, float* __restrict__ partial) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t z = blockIdx.y;
+  if (c >= C) return;
+  const int64_t r0 = z * rows_per, r1 = min(M, r0 + rows_per);
+  auto widen = [](uint16_t h) { return __uint_as_float((uint32_t)h << 16); };
+  float s = 0.0f;
+  int64_t r = r0;
+  for (; r + 8 <= r1; r += 8) {
+    uint16_t b[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const uint16_t v = g[(r + u) * ldg + c];
+      b[u] = widen(relu_out[(r + u) * ldo + c]) > 0.0f ? v : (uint16_t)0;
+    }
+    if (g_eff16) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) g_eff16[(r + u) * lde + c] = b[u];
+    }
+    if (g_eff32) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) g_eff32[(r + u) * C + c] = widen(b[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += widen(b[u]);
+  }
+  for (; r < r1; ++r) {
+    const uint16_t v = g[r * ldg + c];
+    const uint16_t b = widen(relu_out[r * ldo + c]) > 0.0f ? v : (uint16_t)0;
+    if (g_eff16) g_eff16[r * lde + c] = b;
+    if (g_eff32) g_eff32[r * C + c] = widen(b);
+    s += widen(b);
+  }
+  if (partial) partial[z * C + c] = s;
+}
+
 // ---------------------------------------------------------------------------
 // Large-tile path for the big GraphConv shapes (M in the millions): 256 x 256
 // block tile, 8 waves (2 along M x 4 along N, each 128 x 64 = 4 x 2 MFMA
@@ -1343,6 +1389,43 @@ extern "C" int grl_relu_grad(const float* g, const float* relu_out, float* g_eff
   // (a 16-B-per-lane variant measured no faster: 0.64 vs 0.61 ms at M = 1M, C = 256)
   hipLaunchKernelGGL(relu_grad_colsum_kernel, dim3((unsigned)ceil_div(C, 256), (unsigned)zs), dim3(256), 0, st, g,
                      relu_out, g_eff, M, (int64_t)C, rows_per, part);
+  GRL_LAUNCH_CHECK();
+  if (db) {
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs,
+                       db);
+    GRL_LAUNCH_CHECK();
+  }
+  return GRL_OK;
+}
+
+extern "C" int grl_relu_grad_bf16(const uint16_t* g, int64_t ldg, const uint16_t* relu_out, int64_t ldo,
+                                  uint16_t* g_eff16, int64_t lde, float* g_eff32, float* db, int64_t M, int32_t C,
+                                  void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  using namespace grl;
+  TraceRange trace_("grl_relu_grad_bf16");
+  GRL_CHECK_ARG(M >= 0 && C >= 0, "grl_relu_grad_bf16: bad sizes");
+  if (C == 0) return GRL_OK;
+  if (M == 0) {  // no rows (an empty node-range shard): nothing to mask, db = 0
+    if (db && hipMemsetAsync(db, 0, (size_t)C * sizeof(float), as_stream(stream)) != hipSuccess)
+      GRL_FAIL(GRL_E_HIP, "grl_relu_grad_bf16: hipMemsetAsync failed");
+    return GRL_OK;
+  }
+  GRL_CHECK_ARG(g && relu_out, "grl_relu_grad_bf16: NULL pointer");
+  GRL_CHECK_ARG(ldg >= C && ldo >= C && (!g_eff16 || lde >= C),
+                "grl_relu_grad_bf16: need ldg, ldo and lde >= C (ldg=%lld ldo=%lld lde=%lld C=%d)", (long long)ldg,
+                (long long)ldo, (long long)lde, C);
+  GRL_CHECK_ARG((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(relu_out) |
+                 reinterpret_cast<uintptr_t>(g_eff16)) % 2 == 0 && reinterpret_cast<uintptr_t>(g_eff32) % 4 == 0,
+                "grl_relu_grad_bf16: g, relu_out and g_eff16 must be 2-B aligned, g_eff32 4-B aligned");
+  const size_t need = grl_relu_grad_workspace_size(M, C);
+  if (db && (!workspace || workspace_bytes < need))
+    GRL_FAIL(GRL_E_WORKSPACE, "grl_relu_grad_bf16: workspace %zu < %zu", workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  const int zs = colsum_splits(M);
+  const int64_t rows_per = ceil_div(std::max<int64_t>(M, 1), zs);
+  float* part = db ? static_cast<float*>(workspace) : nullptr;
+  hipLaunchKernelGGL(relu_grad_bf16_colsum_kernel, dim3((unsigned)ceil_div(C, 256), (unsigned)zs), dim3(256), 0, st, g,
+                     ldg, relu_out, ldo, g_eff16, lde, g_eff32, M, (int64_t)C, rows_per, part);
   GRL_LAUNCH_CHECK();
   if (db) {
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs,

@@ -153,6 +153,10 @@ SIGNATURES = {
     "grl_graphconv_bwd_data": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_vp, _c_i32,
                                         _c_vp, _c_vp, _P(GrlDropEdge), _c_vp, _c_size, _c_vp]),
     "grl_graphconv_bwd_data_shape_ok": (_c_i32, [_c_i64, _c_i32, _c_i32, _c_i32, _c_i32]),
+    "grl_graphconv_bwd_data_bf16_workspace_query": (_c_size, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_i32,
+                                                              _c_vp, _c_i64]),
+    "grl_graphconv_bwd_data_bf16": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_vp, _c_i32,
+                                             _c_vp, _c_i64, _c_vp, _P(GrlDropEdge), _c_vp, _c_size, _c_vp]),
     "grl_graphconv_fwd": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i32, _c_i32, _c_vp,
                                    _P(GrlDropEdge), _c_vp, _c_size, _c_vp]),
     "grl_graphconv_fwd_bf16_workspace_query": (_c_size, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_i32]),
@@ -179,6 +183,8 @@ SIGNATURES = {
                                      _c_vp]),
     "grl_relu_grad_workspace_size": (_c_size, [_c_i64, _c_i32]),
     "grl_relu_grad": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_size, _c_vp]),
+    "grl_relu_grad_bf16": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp,
+                                    _c_size, _c_vp]),
     "grl_linear_bwd_weight_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32]),
     "grl_linear_bwd_weight": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp,
                                        _c_size, _c_vp]),

@@ -267,6 +267,56 @@ def relu_grad(g: torch.Tensor, out, want_db: bool = False):
     return g_eff, None, db
 
 
+def _rows_apart(t: torch.Tensor) -> bool:
+    """Whether a 2-D tensor with unit column stride keeps its rows apart: a
+    row stride of at least its width (an expanded tensor -- row stride 0, as
+    autograd hands out the gradient of a sum over rows -- does not)."""
+    return t.shape[0] <= 1 or t.stride(0) >= t.shape[1]
+
+
+def _ld(t: torch.Tensor) -> int:
+    """The row stride handed to libgrl (a single row's stride means nothing: at least the width)."""
+    return max(t.stride(0), t.shape[1]) if t.shape[0] <= 1 else t.stride(0)
+
+
+def relu_grad_bf16(g: torch.Tensor, out: torch.Tensor, want_db: bool = False, want_f32: bool = False):
+    """(g_eff16, g_eff32, db) of a bfloat16 output gradient g through the
+    ReLU's [out > 0], out the layer's bfloat16 output, in ONE pass over the
+    two (grl_relu_grad_bf16): g_eff16 the selected bf16 gradient (a new
+    contiguous tensor: the one-kernel data gradient's table), g_eff32 its
+    contiguous fp32 copy (want_f32: what the dW GEMM reads) and db (want_db).
+    Selection only, nothing is rounded: g_eff32 and db are bitwise relu_grad's
+    on g.float(), out.float().  g, out: [M, C] with unit column stride and a
+    row stride of at least C."""
+    return _relu_grad_bf16(g, out, want_db, want_f32)
+
+
+def _relu_grad_bf16(g, out, want_db, want_f32, g_eff16=None, want_16=True):
+    """relu_grad_bf16 with the C entry's other forms: `g_eff16` names the
+    tensor to write (strided; g itself masks in place) and want_16=False skips
+    that output."""
+    _require_device(g, "relu_grad_bf16 g")
+    tensors = [g, out] + ([g_eff16] if g_eff16 is not None else [])
+    if any(t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape != g.shape or (t.shape[1] > 0 and t.stride(1) != 1)
+           or not _rows_apart(t) or t.device != g.device for t in tensors):
+        raise _lib.GrlError("relu_grad_bf16: g, the ReLU output and g_eff16 must be 2-D bfloat16 tensors of one "
+                            "shape with unit column stride and a row stride of at least their width (an expanded "
+                            "tensor: .contiguous() first)")
+    M, C = g.shape
+    if want_16 and g_eff16 is None:
+        g_eff16 = torch.empty(M, C, dtype=torch.bfloat16, device=g.device)
+    if not want_16:
+        g_eff16 = None
+    g_eff32 = torch.empty(M, C, dtype=torch.float32, device=g.device) if want_f32 else None
+    db = torch.empty(C, dtype=torch.float32, device=g.device) if want_db else None
+    ws_bytes = _lib.lib().grl_relu_grad_workspace_size(M, C) if want_db else 0
+    ws = _workspace(ws_bytes, g.device)
+    call("grl_relu_grad_bf16", g.data_ptr(), _ld(g), out.data_ptr(), _ld(out), _ptr(g_eff16),
+         _ld(g_eff16) if g_eff16 is not None else 0, _ptr(g_eff32), _ptr(db), M, C, _ptr(ws), ws_bytes,
+         current_stream_handle(g.device))
+    return g_eff16, g_eff32, db
+
+
 def linear_fwd(Z2: torch.Tensor, W: torch.Tensor, b, relu: bool) -> torch.Tensor:
     M, K = Z2.shape
     C = W.shape[1]
@@ -349,21 +399,27 @@ def x6_rows_ok(M: int, N: int, K: int, path_rows: int = 0) -> bool:
     return _lib.lib().grl_linear_fwd_path(int(M), int(K), int(N), int(path_rows)) != 0
 
 
-def _bwd_data_eligible(g: torch.Tensor, graph, W: torch.Tensor, F: int, width: int) -> bool:
+def _bwd_data_eligible(g: torch.Tensor, graph, W: torch.Tensor, F: int, width: int, fresh_g: bool = False) -> bool:
     """Whether the one-kernel data gradient may take g [num_rows, C], W
     [segments * F, C] over `graph` with dX in column blocks at least `width`
     wide: the graphconv_fused_bwd option, a graph that has a typed transpose,
     operands of the layer's shapes, and the library's shape rule
     (grl_graphconv_bwd_data_shape_ok) for the transpose's rows.  Cheap: asked
     before the (cached, once per graph) transpose is built; the workspace
-    query on the transpose then decides."""
+    query on the transpose then decides.  fresh_g (a bf16 g only): what is
+    gathered is a new contiguous tensor of g's shape, so g's own strides are
+    not looked at."""
     if (_lib.get_option("graphconv_fused_bwd") == 0 or isinstance(graph, EdgeBlockedGraph)
             or not graph.transpose_ok):
         return False
     M, C = g.shape
+    # (an fp32 g contiguous; a bf16 g -- the bf16 entry's gradient table -- rows at least C apart)
+    if g.dtype == torch.float32:
+        g_ok = g.is_contiguous()
+    else:
+        g_ok = g.dtype == torch.bfloat16 and (fresh_g or (g.stride(1) == 1 and _rows_apart(g)))
     if (graph.num_cols < graph.num_rows or graph.self_rows != graph.num_rows or M != graph.num_rows
-            or g.dtype != torch.float32 or not g.is_contiguous() or W.dtype != torch.float32
-            or tuple(W.shape) != (graph.segments * F, C)):
+            or not g_ok or W.dtype != torch.float32 or tuple(W.shape) != (graph.segments * F, C)):
         return False
     # (a graph without columns -- an empty node-range shard -- launches nothing, so has no shape to refuse)
     return graph.num_cols == 0 or _lib.lib().grl_graphconv_bwd_data_shape_ok(
@@ -371,7 +427,7 @@ def _bwd_data_eligible(g: torch.Tensor, graph, W: torch.Tensor, F: int, width: i
 
 
 def graph_conv_bwd_data(g: torch.Tensor, graph: TypedGraph, W: torch.Tensor, F: int, relu_out=None,
-                        want_aggregate: bool = False):
+                        want_aggregate: bool = False, out: torch.Tensor = None):
     """dX of one GraphConv layer in one kernel (grl_graphconv_bwd_data):
     dX = sum_s (A_drop,s^T g) W_s^T over the graph's typed transpose, for g
     the output gradient ([num_rows, C]; through the ReLU's [relu_out > 0]
@@ -381,31 +437,98 @@ def graph_conv_bwd_data(g: torch.Tensor, graph: TypedGraph, W: torch.Tensor, F: 
     then runs dZ = g W^T and the CSC gather).  The graphconv_fused_bwd path
     option 0 disables it.  want_aggregate: return (dX, G_agg, g_eff) with G_agg =
     [A_drop,s^T g_eff]_s ([num_cols, segments * C], written by the same
-    kernel) and g_eff the gradient through the ReLU, for dW_s = X^T G_agg_s."""
+    kernel) and g_eff the gradient through the ReLU, for dW_s = X^T G_agg_s.
+    A bfloat16 g (2-D, unit column stride, any row stride: a column slice of a
+    wider table is gathered in place) takes grl_graphconv_bwd_data_bf16: the
+    gather reads half the bytes and dX is returned in bfloat16, bitwise the
+    fp32 dX on g.float() rounded to nearest even, G_agg (fp32) bitwise that
+    call's.  None where that entry's workspace query is 0 (also: the
+    graphconv_bwd_bf16 path option 0); the caller then widens g.
+    out (a bfloat16 g only): the dX to write, a bfloat16 [num_cols, F] tensor
+    with unit column stride and any row stride (a column-slice view is written
+    in place, the columns beside it untouched; two column blocks are stored
+    straight into it).  An fp32 g with an out, or a bfloat16 g with an fp32
+    out, raises GrlError."""
+    # A bf16 g through a ReLU: what the kernel gathers is the masked copy made below, a new contiguous
+    # tensor, so the query is asked for such a tensor, not for g (whose rows it never reads) -- and before the
+    # mask pass, which an ineligible call then does not run.  (An fp32 g: the query on g, as ever; its masked
+    # copy is contiguous like the g the rule asks for, and as aligned as any new tensor.)
+    plan = _bwd_data_plan(g, graph, W, F, out, fresh_g=relu_out is not None and g.dtype == torch.bfloat16)
+    if plan is None:
+        return None
+    if relu_out is not None:  # (exact on bf16 too: a selection)
+        g = torch.where(relu_out > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
+    return _bwd_data_run(plan, g, graph, W, F, want_aggregate)
+
+
+# What a workspace query is asked for a tensor that does not exist yet: torch's device allocator hands out
+# blocks aligned to 512 B, which every alignment rule of the library divides, and a new [R, W] tensor's row
+# stride is W.  (_bwd_data_run's launch would refuse, not misread, a tensor that broke this.)
+_FRESH_ADDRESS = 512
+
+
+def _bwd_data_plan(g: torch.Tensor, graph, W: torch.Tensor, F: int, out: torch.Tensor = None, fresh_g: bool = False):
+    """What graph_conv_bwd_data launches for these operands -- (csr, eid,
+    column bounds, workspace bytes, out) -- or None outside the one-kernel
+    path.  No device memory is allocated: the workspace query that decides
+    looks at addresses and row strides only, so a dX that _bwd_data_run will
+    allocate (out None) is asked as a new tensor, and so is a bf16 g with
+    fresh_g -- the caller launches on a new contiguous [num_rows, C] tensor it
+    makes once the plan stands (the masked gradient), not on g."""
+    if g.dim() != 2:
+        raise _lib.GrlError(f"graph_conv_bwd_data: g must be 2-D (got {tuple(g.shape)})")
+    bf16 = g.dtype == torch.bfloat16
+    rows = graph.num_cols  # dX rows: every column of the graph (a shard's halo rows get partials)
+    if out is not None:
+        if out.dtype != g.dtype or not bf16:
+            raise _lib.GrlError(f"graph_conv_bwd_data: g is {g.dtype} and out {out.dtype}: out= is a bfloat16 dX "
+                                "for a bfloat16 g (there is no mixed form; an fp32 g returns a new fp32 dX)")
+        if (tuple(out.shape) != (rows, F) or out.device != g.device or (F > 0 and out.stride(1) != 1)
+                or not _rows_apart(out)):
+            raise _lib.GrlError(f"graph_conv_bwd_data: out must be a bfloat16 {(rows, F)} tensor on {g.device} "
+                                "with unit column stride and a row stride of at least F")
     M, C = g.shape
-    S = graph.segments
     nblk = -(-F // FUSED_MAX_OUT)
     wblk = (-(-F // nblk) + 3) // 4 * 4 if nblk > 1 else F  # block width, a multiple of 4
     bounds = [(f0, min(F, f0 + wblk)) for f0 in range(0, F, wblk)]
-    if nblk > 2 or not _bwd_data_eligible(g, graph, W, F, min(b - a for a, b in bounds)):  # (at most two blocks)
+    if nblk > 2 or not _bwd_data_eligible(g, graph, W, F, min(b - a for a, b in bounds),
+                                          fresh_g=fresh_g and bf16):  # (at most two blocks)
         return None
     gt, eid = graph.typed_transpose()
     gt = gt.with_dropedge(graph.dropedge)
     csr = gt.csr_c(C)
-    ws_bytes = _lib.lib().grl_graphconv_bwd_data_workspace_query(ctypes.byref(csr), g.data_ptr(), g.stride(0), C,
-                                                                 W.data_ptr(), bounds[0][1])
-    if ws_bytes == 0:
-        return None
-    if relu_out is not None:
-        g = torch.where(relu_out > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
+    if not bf16:
+        ws_bytes = _lib.lib().grl_graphconv_bwd_data_workspace_query(ctypes.byref(csr), g.data_ptr(), g.stride(0), C,
+                                                                     W.data_ptr(), bounds[0][1])
+        return (csr, eid, bounds, ws_bytes, None) if ws_bytes else None
+    g_at, ldg = (_FRESH_ADDRESS, C) if fresh_g else (g.data_ptr(), _ld(g))
+    dx_at, lddx = (_FRESH_ADDRESS, F) if out is None else (out.data_ptr(), _ld(out))
+    sizes = [_lib.lib().grl_graphconv_bwd_data_bf16_workspace_query(
+        ctypes.byref(csr), g_at, ldg, C, W.data_ptr(), f1 - f0, dx_at + 2 * f0, lddx) for f0, f1 in bounds]
+    return (csr, eid, bounds, max(sizes), out) if min(sizes) else None
+
+
+def _bwd_data_run(plan, g: torch.Tensor, graph, W: torch.Tensor, F: int, want_aggregate: bool = False):
+    """The launches of a _bwd_data_plan for g (the gradient through the ReLU;
+    where the plan was asked with fresh_g, the new contiguous tensor)."""
+    csr, eid, bounds, ws_bytes, dX = plan
+    M, C = g.shape
+    S = graph.segments
+    bf16 = g.dtype == torch.bfloat16
+    rows = graph.num_cols
+    if dX is None:
+        dX = torch.empty(rows, F, dtype=g.dtype, device=g.device)
     ws = _workspace(ws_bytes, g.device)
     stream = current_stream_handle(g.device)
-    rows = graph.num_cols  # dX rows: every column of the graph (a shard's halo rows get partials)
-    dX = torch.empty(rows, F, dtype=torch.float32, device=g.device)
     G_agg = torch.empty(rows, S * C, dtype=torch.float32, device=g.device) if want_aggregate else None
     for i, (f0, f1) in enumerate(bounds):
         w = f1 - f0
         Wb = W.contiguous() if len(bounds) == 1 else W.reshape(S, F, C)[:, f0:f1, :].reshape(S * w, C).contiguous()
+        if bf16:  # strided stores: a column block goes straight into dX[:, f0:f1]
+            call("grl_graphconv_bwd_data_bf16", ctypes.byref(csr), eid.data_ptr(), g.data_ptr(), _ld(g), M, C,
+                 Wb.data_ptr(), w, dX.data_ptr() + 2 * f0, _ld(dX), _ptr(G_agg) if i == 0 else None,
+                 _de_ref(graph), ws.data_ptr(), ws_bytes, stream)
+            continue
         out = dX if len(bounds) == 1 else torch.empty(rows, w, dtype=torch.float32, device=g.device)
         call("grl_graphconv_bwd_data", ctypes.byref(csr), eid.data_ptr(), g.data_ptr(), g.stride(0), M, C,
              Wb.data_ptr(), w, out.data_ptr(), _ptr(G_agg) if i == 0 else None, _de_ref(graph), ws.data_ptr(),
@@ -437,7 +560,7 @@ def graph_conv_bwd_data_rows_views(g: torch.Tensor, graph: TypedGraph, W: torch.
     is outside the one-kernel path.  No device work beyond the cached
     transpose and split plans: a caller that must decide collectively
     (grl.dist rows_backward) asks this first, agrees, then launches."""
-    if not _bwd_data_eligible(g, graph, W, F, F):
+    if g.dtype != torch.float32 or not _bwd_data_eligible(g, graph, W, F, F):  # (row blocks: the fp32 entry only)
         return None
     C = g.shape[1]
     for r0, r1 in blocks:
@@ -503,7 +626,10 @@ class _GraphConv(torch.autograd.Function):
     (robust_gcn.py:45-51), as one autograd node: the same kernels and
     results as typed_aggregate + graph_linear.  X float32 or bfloat16 (the
     bf16-table forward entries; the backward is the fp32 layer's on the fp32
-    Z and output gradient, dX rounded once to X's dtype).  (Running dW on a second HIP
+    Z and output gradient, dX rounded once to X's dtype -- and with a bf16
+    output gradient too, where grl_graphconv_bwd_data_bf16 applies, the data
+    gradient gathers that gradient as stored and writes the bf16 dX itself,
+    the same bits with no widened copy: _backward_bf16).  (Running dW on a second HIP
     stream beside dZ / the transposed gather was measured and bought nothing:
     39-41 ms per C3 layer either way, each kernel already fills the chip.)"""
 
@@ -534,6 +660,11 @@ class _GraphConv(torch.autograd.Function):
         Z, W, out = ctx.saved_tensors
         want_w = ctx.needs_input_grad[2]
         want_b = ctx.has_b and ctx.needs_input_grad[3]
+        if (g.dtype == torch.bfloat16 and ctx.xdtype == torch.bfloat16 and ctx.needs_input_grad[0]
+                and not isinstance(ctx.graph, EdgeBlockedGraph)):
+            res = _GraphConv._backward_bf16(ctx, g, Z, W, out, want_w, want_b)
+            if res is not None:
+                return res
         # a bf16 out hands back a bf16 g: the fp32 layer's backward on g.float(), the ReLU mask from the bf16
         # out ([out > 0] survives the rounding); both widened to fp32 here
         g, mask, db_pre = relu_grad(g.contiguous().float(), out.float() if ctx.relu else None, want_b)
@@ -564,6 +695,48 @@ class _GraphConv(torch.autograd.Function):
             dX = dX.view(ctx.xshape).to(ctx.xdtype)  # a bf16 X: the fp32 dX rounded once
         if want_w or (want_b and db_pre is None):
             dW, db = linear_bwd_weight(Z, g, mask, want_b and db_pre is None)
+        if db_pre is not None:
+            db = db_pre
+        return dX, None, dW if want_w else None, db, None, None, None
+
+    @staticmethod
+    def _backward_bf16(ctx, g: torch.Tensor, Z, W: torch.Tensor, out, want_w: bool, want_b: bool):
+        """The backward of a bf16 X under a bf16 output gradient where
+        grl_graphconv_bwd_data_bf16 applies (else None, and backward runs the
+        widened path): the data gradient gathers the bf16 gradient as stored and
+        writes the bf16 dX, so g.float(), out.float() and an fp32 [N, F] dX
+        never exist.  From PREMASK_ROWS rows one grl_relu_grad_bf16 pass makes
+        the masked bf16 gradient, db, and -- only when dW wants it -- the fp32
+        g_eff the dW GEMM reads.  Every gradient is bitwise the widened path's."""
+        graph, F = ctx.graph, ctx.xshape[-1]
+        g2 = g.reshape(-1, g.shape[-1])
+        M, C = g2.shape
+        relu = ctx.relu
+        premask = relu and M >= PREMASK_ROWS
+        # With a ReLU the kernel gathers the masked gradient, a new contiguous tensor made once the plan
+        # stands; without one it gathers g as handed over, unless autograd handed over an expanded gradient
+        # (row stride 0: the gradient of a sum over nodes) or one without unit column stride, which is copied.
+        as_is = not relu and g2.stride(1) == 1 and _rows_apart(g2)
+        plan = _bwd_data_plan(g2, graph, W, F, fresh_g=not as_is)
+        if plan is None:
+            return None
+        if not (g2.stride(1) == 1 and _rows_apart(g2)):
+            g2 = g2.contiguous()
+        g32 = mask = db_pre = None
+        if premask:
+            g16, g32, db_pre = _relu_grad_bf16(g2, out, want_b, want_w)
+        else:
+            g16 = torch.where(out > 0, g2, torch.zeros((), dtype=g2.dtype, device=g.device)) if relu else g2
+        dX = _bwd_data_run(plan, g16, graph, W, F).view(ctx.xshape)
+        del g16
+        dW = db = None
+        if want_w or (want_b and db_pre is None):
+            if not premask:  # the dW GEMM reads fp32 (and masks on its loads below PREMASK_ROWS)
+                g32 = g2.float().contiguous()
+                mask = out.float() if relu else None
+            if ctx.recompute:
+                Z = spmm_forward(Z, graph)
+            dW, db = linear_bwd_weight(Z, g32, mask, want_b and db_pre is None)
         if db_pre is not None:
             db = db_pre
         return dX, None, dW if want_w else None, db, None, None, None
@@ -667,10 +840,18 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
     torch.float32: the fp32 output as ever): a new contiguous bfloat16 tensor
     written by the kernel's epilogue (grl_graphconv_fwd[_train]_bf16_to_bf16),
     bitwise the fp32 output rounded to nearest even, from the same one
-    autograd node.  Autograd then hands the node a bfloat16 output gradient;
-    the backward is the fp32 layer's on g.float() with the ReLU mask taken
-    from the bfloat16 output, dX rounded once as above.  recompute=True keeps
-    the bf16 X and re-aggregates Z, as above."""
+    autograd node.  Autograd then hands the node a bfloat16 output gradient.
+    Where the one-kernel data gradient takes it as stored
+    (grl_graphconv_bwd_data_bf16: a nonzero workspace query, the
+    graphconv_bwd_bf16 path option on) the backward gathers the bf16 gradient
+    rows -- half the bytes -- and writes the bf16 X.grad from the kernel's
+    epilogue; from PREMASK_ROWS rows one pass (grl_relu_grad_bf16) applies the
+    ReLU mask of the bfloat16 output, sums db and, only if dW is wanted, makes
+    the fp32 gradient the dW GEMM reads.  No g.float(), out.float() or fp32
+    [N, F] dX exists there.  Elsewhere the backward is the fp32 layer's on
+    g.float() with the ReLU mask taken from the bfloat16 output, dX rounded
+    once as above.  X.grad, dW and db are the same bits either way.
+    recompute=True keeps the bf16 X and re-aggregates Z, as above."""
     if X.dtype not in _TABLE_DTYPES:
         raise _lib.GrlError(f"graph_conv: node features must be float32 or bfloat16 (got {X.dtype})")
     if W.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):

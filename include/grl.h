@@ -423,7 +423,8 @@ int grl_graphconv_fwd_train(const GrlTypedCsr* g, const float* X, int64_t ldx,
  * row-chunked form).  graphconv_fused = 0 and ws_spin apply as to the fp32
  * entries; a bounded wait that runs out poisons out (and Z) and is reported
  * by grl_check() under these entries' own names.  The data gradient is the
- * fp32 layer's (grl_graphconv_bwd_data on the fp32 output gradient).       */
+ * fp32 layer's (grl_graphconv_bwd_data on the fp32 output gradient), or,
+ * for a bf16 output gradient and a bf16 dX, grl_graphconv_bwd_data_bf16.    */
 size_t grl_graphconv_fwd_bf16_workspace_query(const GrlTypedCsr* g,
                                               const uint16_t* X, int64_t ldx,
                                               int32_t F, const float* W,
@@ -462,8 +463,9 @@ int grl_graphconv_fwd_train_bf16(const GrlTypedCsr* g, const uint16_t* X,
  * K, C, g->path_rows).  A smaller workspace: GRL_E_WORKSPACE.
  * GRL_E_INVALID, decided on the host: the _bf16 entries' checks, NULL out,
  * ldo < C, X or out not 2 B-aligned (the query answers 0 for ldo < C).
- * There is no fp32-table form and no data-gradient form with a bf16 output:
- * a model's first table is cast once by the caller.  A bounded wait that runs
+ * There is no fp32-table form with a bf16 output: a model's first table is
+ * cast once by the caller.  (The data-gradient form with a bf16 output is
+ * grl_graphconv_bwd_data_bf16, over a bf16 gradient table.)  A bounded wait that runs
  * out fills out's C columns of every row (and Z) with NaN and is reported by
  * grl_check() under these entries' names.                                  */
 size_t grl_graphconv_fwd_bf16_to_bf16_workspace_query(
@@ -530,6 +532,45 @@ int32_t grl_graphconv_bwd_data_shape_ok(int64_t rows, int32_t num_types,
                                         int32_t has_self, int32_t C,
                                         int32_t F);
 
+/* grl_graphconv_bwd_data over a gradient table of bf16 bits, writing a bf16
+ * dX: the backward of a layer whose output (and so output gradient) is bf16.
+ * G holds bf16 bits, row n at G + n * ldg (ldg >= C, counted in bf16
+ * elements); dX holds bf16 bits, row m at dX + m * lddx (lddx >= F).  W and
+ * G_agg are fp32 as in the fp32 entry; gt, eid, g_rows and de mean what they
+ * mean there.
+ *   dX is BITWISE the round-to-nearest-even bf16 of what
+ *   grl_graphconv_bwd_data writes for the widened G (widening is exact, the
+ *   fmaf chains and MFMA products are the same, one rounding in the
+ *   epilogue); G_agg is bitwise that entry's.
+ * Columns of a dX row outside [0, F) are never written; G and dX may be
+ * disjoint column ranges of one allocation (overlapping ranges: undefined).
+ * One kernel (the persistent form's data-gradient instance with the bf16
+ * table's 8 B gather loads and the bf16 output's packed dword stores), and
+ * only that: eligible is a nonzero workspace query, which holds when
+ * grl_graphconv_bwd_data_shape_ok does, gt->self_row0 == 0, W is 16 B-aligned,
+ * G is 8 B-aligned with ldg % 4 == 0 and ldg < 2^31, dX is 4 B-aligned with
+ * lddx % 2 == 0, there is no heavy-row split plan, nnz < 2^31 and the path
+ * option graphconv_bwd_bf16 is 1 (0: the query answers 0).  The answer is the
+ * size of W's planes plus the status word, the fp32 query's bytes.  Other
+ * shapes: GRL_E_UNSUPPORTED -- there is no second path inside the library;
+ * the caller widens G and runs grl_graphconv_bwd_data.
+ * GRL_E_INVALID, decided on the host: the fp32 entry's checks, a NULL dX,
+ * lddx < F, ldg < C, an odd G or dX address, a G_agg that is not 16 B-aligned
+ * (the query answers 0 for a NULL dX, lddx < F and ldg < C).  gt->num_rows
+ * == 0 and a shard's empty operands are accepted as there.  A missing,
+ * unaligned or short workspace: GRL_E_WORKSPACE.  A bounded wait that runs
+ * out fills dX's F columns of every row (and G_agg) with NaN and is reported
+ * by grl_check() under this entry's name.                                   */
+size_t grl_graphconv_bwd_data_bf16_workspace_query(
+    const GrlTypedCsr* gt, const uint16_t* G, int64_t ldg, int32_t C,
+    const float* W, int32_t F, const uint16_t* dX, int64_t lddx);
+int grl_graphconv_bwd_data_bf16(const GrlTypedCsr* gt, const int32_t* eid,
+                                const uint16_t* G, int64_t ldg, int64_t g_rows,
+                                int32_t C, const float* W, int32_t F,
+                                uint16_t* dX, int64_t lddx, float* G_agg,
+                                const GrlDropEdge* de, void* workspace,
+                                size_t workspace_bytes, grl_stream_t stream);
+
 /* Backward of grl_linear_fwd (autograd MmBackward0 of robust_gcn.py:50, with
  * the ReLU of drop_robust_gcn.py:76 folded in when relu_out != NULL):
  *   dZ = (g * [relu_out > 0]) W^T           grl_linear_bwd_data,  dZ [M, K] (ld lddz)
@@ -563,6 +604,23 @@ size_t grl_relu_grad_workspace_size(int64_t M, int32_t C);
 int grl_relu_grad(const float* g, const float* relu_out, float* g_eff, float* db,
                   int64_t M, int32_t C, void* workspace, size_t workspace_bytes,
                   grl_stream_t stream);
+
+/* grl_relu_grad for a bf16 output gradient and a bf16 ReLU output (bf16 bits;
+ * rows ldg / ldo >= C elements apart), both read once.  Each output may be
+ * NULL:
+ *   g_eff16 = relu_out > 0 ? g : +0   bf16 bits, rows lde >= C apart; may
+ *                                     alias g (grl_graphconv_bwd_data_bf16's G)
+ *   g_eff32 = the same, widened       fp32 [M, C] contiguous (the dW GEMM's)
+ *   db      = sum over rows of it
+ * A selection: nothing is rounded.  db is summed in grl_relu_grad's row blocks
+ * and order, so db and g_eff32 are bitwise grl_relu_grad's db and g_eff on the
+ * widened operands.  Workspace (db only): grl_relu_grad_workspace_size(M, C).
+ * M == 0 writes db = 0, C == 0 returns GRL_OK, as there.                    */
+int grl_relu_grad_bf16(const uint16_t* g, int64_t ldg, const uint16_t* relu_out,
+                       int64_t ldo, uint16_t* g_eff16, int64_t lde,
+                       float* g_eff32, float* db, int64_t M, int32_t C,
+                       void* workspace, size_t workspace_bytes,
+                       grl_stream_t stream);
 
 /* emb1: Linear(K -> C) (+ReLU) over sparse bag-of-characters rows
  * (drop_robust_gcn.py:36,64; rows from TextlineEncoding,
