@@ -470,6 +470,31 @@ __global__ __launch_bounds__(256) void relu_grad_bf16_colsum_kernel(const uint16
   if (partial) partial[z * C + c] = s;
 }
 
+// colsum_partial_kernel over bf16 bits with rows ldg apart and no mask
+// (grl_linear_bwd_weight_bf16g's db): the same row blocks, each value widened
+// (exact) and added in the same order, so db is bitwise that kernel's on the
+// widened g.
+__global__ __launch_bounds__(256) void colsum_partial_bf16_kernel(const uint16_t* __restrict__ g, int64_t ldg,
+                                                                   int64_t M, int64_t C, int64_t rows_per,
+                                                                   float* __restrict__ partial) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t z = blockIdx.y;
+  if (c >= C) return;
+  const int64_t r0 = z * rows_per, r1 = min(M, r0 + rows_per);
+  auto widen = [](uint16_t h) { return __uint_as_float((uint32_t)h << 16); };
+  float s = 0.0f;
+  int64_t r = r0;
+  for (; r + 8 <= r1; r += 8) {
+    uint16_t b[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) b[u] = g[(r + u) * ldg + c];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += widen(b[u]);
+  }
+  for (; r < r1; ++r) s += widen(g[r * ldg + c]);
+  partial[z * C + c] = s;
+}
+
 // ---------------------------------------------------------------------------
 // Large-tile path for the big GraphConv shapes (M in the millions): 256 x 256
 // block tile, 8 waves (2 along M x 4 along N, each 128 x 64 = 4 x 2 MFMA
@@ -1004,6 +1029,155 @@ __global__ __launch_bounds__(512) void gemm_x6t_kernel(GemmArgs p) {
   }
 }
 
+// ---------------------------------------------------------------------------
+// x3t: gemm_x6t_kernel for a g stored as bf16 (grl_linear_bwd_weight_bf16g,
+// DESIGN.md §4.19).  g16(k, n) = bf16 bits at g16[k * p.ldb + n] (p.B unused).
+// A bf16 g is one plane, so its rows go into LDS as loaded (8 B a lane per
+// staged row, no split VALU), a stage is 3 A planes + 1 B plane (2 x 32 KB),
+// B costs 2 fragment reads a step instead of 6 and every accumulator block
+// three plane products instead of six (x3_mfma).  The tile, the K16 steps, the
+// stages' swizzle, the staging one step ahead, the zeroing of rows past the
+// split's end, the epilogue and the host's split rule are gemm_x6t_kernel's,
+// so every dW element is summed in its order: the bits are that kernel's on
+// the widened g.  Preconditions (x3t_ok): A 16 B-aligned with lda % 4 == 0,
+// g16 8 B-aligned with ldb % 4 == 0, M, N multiples of 4.
+constexpr int X3_STAGE = 4 * X6_PLANE;  // three A planes, then B's one
+
+template <int EPI>
+__global__ __launch_bounds__(512) void gemm_x3t_kernel(GemmArgs p, const uint16_t* __restrict__ g16) {
+  __shared__ __attribute__((aligned(16))) uint16_t smem[2 * X3_STAGE];  // 2 stages x (3 A + 1 B) planes x 8 KB
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;
+  const int l32 = lane & 31, h = lane >> 5;
+  int64_t mi, ni, zi;
+  tile_of(p, mi, ni, zi);
+  const int64_t m0 = mi * LB_M, n0 = ni * LB_N;
+  const int64_t kbeg = zi * p.k_per_split;
+  const int64_t kend = min(p.K, kbeg + p.k_per_split);
+  const int64_t nk = kend > kbeg ? (kend - kbeg + X6_K - 1) / X6_K : 0;
+
+  // staging: 4-column group f = tid + 512 i of each operand: k row f >> 6, columns (f & 63) * 4 (a float4 of
+  // A, a uint2 = 4 bf16 of g); the staged k rows are wave-uniform, as in gemm_x6t_kernel
+  const int kr0 = __builtin_amdgcn_readfirstlane(tid >> 6), kr1 = kr0 + 8;
+  const int col = (tid & 63) * 4;
+  const int64_t am = min<int64_t>(m0 + col, p.M - 4), bn = min<int64_t>(n0 + col, p.N - 4);
+  const float* __restrict__ a_base = p.A + am;
+  const uint16_t* __restrict__ b_base = g16 + bn;
+  const int st_off0 = kr0 * 256 + (col ^ ((kr0 & 3) << 5));
+  const int st_off1 = kr1 * 256 + (col ^ ((kr1 & 3) << 5));
+  float4 ra0, ra1;
+  uint2 rb0, rb1;
+  bool in0, in1;  // the staged rows lie inside this split's K range
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const uint2 zero2 = make_uint2(0u, 0u);
+  // rows past the split's end: loaded clamped (from kbeg), zeroed when stashed (gemm_x6t_kernel's reason)
+#define X3T_LOAD(t)                                                                                       \
+  do {                                                                                                    \
+    const int64_t k_ = kbeg + (t) * X6_K;                                                                 \
+    in0 = k_ + kr0 < kend;                                                                                \
+    in1 = k_ + kr1 < kend;                                                                                \
+    const int64_t r0_ = in0 ? k_ + kr0 : kbeg;                                                            \
+    const int64_t r1_ = in1 ? k_ + kr1 : kbeg;                                                            \
+    ra0 = *reinterpret_cast<const float4*>(a_base + r0_ * p.lda);                                         \
+    ra1 = *reinterpret_cast<const float4*>(a_base + r1_ * p.lda);                                         \
+    rb0 = *reinterpret_cast<const uint2*>(b_base + r0_ * p.ldb);                                          \
+    rb1 = *reinterpret_cast<const uint2*>(b_base + r1_ * p.ldb);                                          \
+  } while (0)
+#define X3T_SPLIT(v, base, off)                                                                           \
+  do {                                                                                                    \
+    uint2 q0_, q1_, q2_;                                                                                  \
+    split3(v, q0_, q1_, q2_);                                                                             \
+    *reinterpret_cast<uint2*>((base) + (off)) = q0_;                                                      \
+    *reinterpret_cast<uint2*>((base) + X6_PLANE + (off)) = q1_;                                           \
+    *reinterpret_cast<uint2*>((base) + 2 * X6_PLANE + (off)) = q2_;                                       \
+  } while (0)
+#define X3T_STASH(st)                                                                                     \
+  do {                                                                                                    \
+    if (!in0) ra0 = zero4, rb0 = zero2; /* wave-uniform: only a split's last K16 step branches */         \
+    if (!in1) ra1 = zero4, rb1 = zero2;                                                                   \
+    X3T_SPLIT(ra0, (st), st_off0);                                                                        \
+    X3T_SPLIT(ra1, (st), st_off1);                                                                        \
+    *reinterpret_cast<uint2*>((st) + 3 * X6_PLANE + st_off0) = rb0;                                       \
+    *reinterpret_cast<uint2*>((st) + 3 * X6_PLANE + st_off1) = rb1;                                       \
+  } while (0)
+
+  // this lane's transposed-read coordinates: k = 8h + ((lane & 15) >> 2),
+  // column = block base + 16 ((lane >> 4) & 1) + 4 (lane & 3)
+  const int tk = 8 * h + ((lane & 15) >> 2);
+  const int tc = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+
+  if (nk > 0) {
+    X3T_LOAD(0);
+    X3T_STASH(smem);
+    if (nk > 1) X3T_LOAD(1);
+  }
+  __syncthreads();
+  {
+    const lds_u16* s3 = (const lds_u16*)smem;
+    const int sx = (tk & 3) << 5;
+    int oa[4], ob[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) oa[i] = tk * 256 + ((wm * 128 + i * 32 + tc) ^ sx);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) ob[j] = tk * 256 + ((wn * 64 + j * 32 + tc) ^ sx);
+    // step t reads LDS stage S = t & 1 (a constant of the body: the loop is unrolled by two) and stashes the
+    // staged rows of step t + 1 into the other stage
+    auto step = [&](int64_t t, auto stage) {
+      constexpr int S = decltype(stage)::value;
+      const lds_u16* cur = s3 + S * X3_STAGE;
+      auto frag = [](const lds_u16* p0) { return tr8s(p0, p0 + 4 * 256); };  // (second block row: 4 k rows on)
+      bf16x8_t a_[4][3], b_[2];
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a_[i][q] = frag(cur + q * X6_PLANE + oa[i]);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) b_[j] = frag(cur + 3 * X6_PLANE + ob[j]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) x3_mfma(acc[i][j], a_[i], b_[j]);
+      if (t + 1 < nk) {
+        X3T_STASH(smem + (S ^ 1) * X3_STAGE);  // the other stage: last read in step t-1
+        if (t + 2 < nk) X3T_LOAD(t + 2);
+      }
+      __syncthreads();
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    int64_t t = 0;
+    for (; t + 1 < nk; t += 2) {
+      step(t, I0{});
+      step(t + 1, I1{});
+    }
+    if (t < nk) step(t, I0{});
+  }
+#undef X3T_LOAD
+#undef X3T_SPLIT
+#undef X3T_STASH
+  float* Cz = p.C + (EPI == EPI_SLAB ? zi * p.M * p.ldc : 0);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int64_t gn = n0 + wn * 64 + j * 32 + l32;
+    if (gn >= p.N) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t gm = m0 + wm * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (gm < p.M) Cz[gm * p.ldc + gn] = acc[i][j][r];
+      }
+  }
+}
+
 constexpr int GEMM_BK = 32;
 
 template <bool A_KC, bool B_KC, int EPI, int TBN = BN>
@@ -1500,6 +1674,89 @@ extern "C" int grl_linear_bwd_weight(const float* Z, int64_t ldz, const float* g
     const int64_t rows_per = ceil_div(std::max<int64_t>(M, 1), zs);
     hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)ceil_div(C, 256), (unsigned)zs), dim3(256), 0, st, g,
                        relu_out, M, C, rows_per, part);
+    GRL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs,
+                       db);
+    GRL_LAUNCH_CHECK();
+  }
+  return GRL_OK;
+}
+
+namespace grl {
+namespace {
+// x3t (dW from a g stored as bf16) selection: gemm_x6t_kernel's shape rule, Z
+// as that kernel loads it (16 B), g's rows on the 8 B loads of four bf16, and
+// the dw_bf16g path option
+bool x3t_ok(const float* Z, int64_t ldz, const uint16_t* g, int64_t ldg, int64_t M, int64_t K, int64_t C) {
+  return opt(OPT_DW_BF16G) != 0 && x6t_shape_ok(M, K, C) && al16(Z) && ldz % 4 == 0 &&
+         reinterpret_cast<uintptr_t>(g) % 8 == 0 && ldg % 4 == 0;
+}
+}  // namespace
+}  // namespace grl
+
+extern "C" size_t grl_linear_bwd_weight_bf16g_workspace_query(const float* Z, int64_t ldz, const uint16_t* g,
+                                                              int64_t ldg, int64_t M, int32_t K, int32_t C) {
+  if (!Z || !g || M <= 0 || K <= 0 || C <= 0 || ldz < K || ldg < C) return 0;
+  return grl::x3t_ok(Z, ldz, g, ldg, M, K, C) ? grl_linear_bwd_weight_workspace_size(M, K, C) : 0;
+}
+
+extern "C" int grl_linear_bwd_weight_bf16g(const float* Z, int64_t ldz, const uint16_t* g, int64_t ldg, float* dW,
+                                           float* db, int64_t M, int32_t K, int32_t C, void* workspace,
+                                           size_t workspace_bytes, grl_stream_t stream) {
+  TraceRange trace_("grl_linear_bwd_weight_bf16g");
+  GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0, "grl_linear_bwd_weight_bf16g: negative size");
+  GRL_CHECK_ARG(ldz >= K && ldg >= C,
+                "grl_linear_bwd_weight_bf16g: need ldz >= K and ldg >= C (ldz=%lld K=%d ldg=%lld C=%d)", (long long)ldz,
+                K, (long long)ldg, C);
+  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(g) % 2 == 0, "grl_linear_bwd_weight_bf16g: g must be 2-B aligned");
+  if (K == 0 || C == 0) return GRL_OK;
+  if (M == 0) {  // no rows (an empty node-range shard): dW = 0, db = 0
+    GRL_CHECK_ARG(dW, "grl_linear_bwd_weight_bf16g: NULL pointer");
+    hipStream_t st = as_stream(stream);
+    if (hipMemsetAsync(dW, 0, (size_t)K * C * sizeof(float), st) != hipSuccess ||
+        (db && hipMemsetAsync(db, 0, (size_t)C * sizeof(float), st) != hipSuccess))
+      GRL_FAIL(GRL_E_HIP, "grl_linear_bwd_weight_bf16g: hipMemsetAsync failed");
+    return GRL_OK;
+  }
+  GRL_CHECK_ARG(Z && g && dW, "grl_linear_bwd_weight_bf16g: NULL pointer");
+  if (!x3t_ok(Z, ldz, g, ldg, M, K, C))
+    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_linear_bwd_weight_bf16g: outside the bf16-gradient dW path (M %lld, K %d, C %d, "
+             "the operands' alignment or the dw_bf16g / gemm_x6 options; see "
+             "grl_linear_bwd_weight_bf16g_workspace_query)", (long long)M, K, C);
+  const size_t need = grl_linear_bwd_weight_workspace_size(M, K, C);
+  if (!workspace || workspace_bytes < need)
+    GRL_FAIL(GRL_E_WORKSPACE, "grl_linear_bwd_weight_bf16g: workspace %zu < %zu", workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  float* slab = static_cast<float*>(workspace);
+  // gemm_x6t_kernel's launch (grl_linear_bwd_weight): the same splits, tile order and slab reduce
+  GemmArgs a = gemm_args(Z, ldz, nullptr, ldg, nullptr, C, K, C, M);
+  const int splits = x6t_splits(M, K, C);
+  a.C = splits > 1 ? slab : dW;
+  a.k_per_split = ceil_div(ceil_div(M, splits), X6_K) * X6_K;
+  const int used = (int)ceil_div(M, a.k_per_split);
+  a.mt = ceil_div(a.M, LB_M);
+  a.nt = ceil_div(a.N, LB_N);
+  a.zt = used;
+  a.inner_n = 0;
+  GRL_CHECK_ARG(a.mt * a.nt * a.zt < 2147483647LL, "gemm: grid too large");
+  const dim3 grid((unsigned)(a.mt * a.nt * a.zt));
+  if (used > 1)
+    hipLaunchKernelGGL(gemm_x3t_kernel<EPI_SLAB>, grid, dim3(512), 0, st, a, g);
+  else
+    hipLaunchKernelGGL(gemm_x3t_kernel<EPI_STORE>, grid, dim3(512), 0, st, a, g);
+  GRL_LAUNCH_CHECK();
+  if (used > 1) {
+    const int64_t n = (int64_t)K * C;
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 65536)), dim3(256), 0,
+                       st, slab, n, used, dW);
+    GRL_LAUNCH_CHECK();
+  }
+  if (db) {
+    const int zs = colsum_splits(M);
+    float* part = slab + (size_t)wgt_slab_splits(M, K, C) * K * C;
+    const int64_t rows_per = ceil_div(std::max<int64_t>(M, 1), zs);
+    hipLaunchKernelGGL(colsum_partial_bf16_kernel, dim3((unsigned)ceil_div(C, 256), (unsigned)zs), dim3(256), 0, st, g,
+                       ldg, M, (int64_t)C, rows_per, part);
     GRL_LAUNCH_CHECK();
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs,
                        db);

@@ -100,6 +100,16 @@ __device__ __forceinline__ void x6_mfma(f32x16& acc, const bf16x8_t (&a)[3], con
   mfma_bf16(acc, a[0], b[0]);
 }
 
+// acc += a b for a split a and a b that is ONE bf16 plane (values stored as
+// bf16: b1 = b2 = 0): x6_mfma's sequence without its three products on a zero
+// plane.  Those add exact zeros to an accumulator that is never -0 (it starts
+// at +0), so the result is bitwise x6_mfma's on the widened b.
+__device__ __forceinline__ void x3_mfma(f32x16& acc, const bf16x8_t (&a)[3], bf16x8_t b) {
+  mfma_bf16(acc, a[2], b);
+  mfma_bf16(acc, a[1], b);
+  mfma_bf16(acc, a[0], b);
+}
+
 // ---- LDS-DMA ----------------------------------------------------------------
 // global -> LDS DMA of one 16 B chunk per lane (lane l lands at lds_base + 16 l).
 // Issued from asm so that hipcc's waitcnt pass neither sees nor waits on it

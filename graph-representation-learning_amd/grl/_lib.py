@@ -188,6 +188,9 @@ SIGNATURES = {
     "grl_linear_bwd_weight_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32]),
     "grl_linear_bwd_weight": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp,
                                        _c_size, _c_vp]),
+    "grl_linear_bwd_weight_bf16g_workspace_query": (_c_size, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32]),
+    "grl_linear_bwd_weight_bf16g": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32,
+                                             _c_vp, _c_size, _c_vp]),
     "grl_dense_to_csr_workspace_size": (_c_size, [_c_i64]),
     "grl_dense_to_csr_rowptr": (_c_i32, [_c_vp, _c_i64, _c_i64, _c_i32, _P(_c_i64), _c_vp, _c_vp, _c_size, _c_vp]),
     "grl_dense_to_csr_fill": (_c_i32, [_c_vp, _c_i64, _c_i64, _c_i32, _P(_c_i64), _c_vp, _c_vp, _c_vp, _c_vp]),

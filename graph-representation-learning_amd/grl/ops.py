@@ -351,6 +351,40 @@ def linear_bwd_weight(Z2: torch.Tensor, g: torch.Tensor, relu_out, want_db: bool
     return dW, db
 
 
+def linear_bwd_weight_bf16(Z2: torch.Tensor, g16: torch.Tensor, want_db: bool):
+    """(dW, db) = (Z2^T g16, column sums of g16) with the bfloat16 gradient read
+    as stored (grl_linear_bwd_weight_bf16g: half the plane products of the
+    split-bf16 dW GEMM, no widened copy), bitwise linear_bwd_weight(Z2,
+    g16.float(), None, want_db) -- or None where that entry's workspace query is
+    0 (below the x6 size floor, g16 off the 8 B grid, the dw_bf16g or gemm_x6
+    path option 0, ...); the caller then widens g16.  Nothing is allocated
+    before the query.  g16: 2-D bfloat16 with unit column stride and a row
+    stride of at least its width (a column slice of a wider table is read in
+    place), already through the ReLU's mask; Z2: [M, K] float32, unit column
+    stride."""
+    _require_device(g16, "linear_bwd_weight_bf16 g")
+    if (g16.dtype != torch.bfloat16 or g16.dim() != 2 or (g16.shape[1] > 0 and g16.stride(1) != 1)
+            or not _rows_apart(g16)):
+        raise _lib.GrlError("linear_bwd_weight_bf16: g must be a 2-D bfloat16 tensor with unit column stride and a row "
+                            "stride of at least its width (an expanded tensor: .contiguous() first)")
+    if (Z2.dtype != torch.float32 or Z2.dim() != 2 or Z2.shape[0] != g16.shape[0] or Z2.device != g16.device
+            or (Z2.shape[1] > 0 and Z2.stride(1) != 1) or not _rows_apart(Z2)):
+        raise _lib.GrlError(f"linear_bwd_weight_bf16: Z must be a float32 [{g16.shape[0]}, K] tensor on {g16.device} "
+                            "with unit column stride")
+    M, K = Z2.shape
+    C = g16.shape[1]
+    ws_bytes = _lib.lib().grl_linear_bwd_weight_bf16g_workspace_query(Z2.data_ptr(), _ld(Z2), g16.data_ptr(), _ld(g16),
+                                                                      M, K, C)
+    if ws_bytes == 0:
+        return None
+    dW = torch.empty(K, C, dtype=torch.float32, device=g16.device)
+    db = torch.empty(C, dtype=torch.float32, device=g16.device) if want_db else None
+    ws = _workspace(ws_bytes, g16.device)
+    call("grl_linear_bwd_weight_bf16g", Z2.data_ptr(), _ld(Z2), g16.data_ptr(), _ld(g16), dW.data_ptr(), _ptr(db), M, K,
+         C, _ptr(ws), ws_bytes, current_stream_handle(g16.device))
+    return dW, db
+
+
 class _GraphLinear(torch.autograd.Function):
     """out = Z W + b [ReLU]; backward on the same MFMA GEMM kernel with the
     ReLU mask fused into the operand loads (no g*mask temporary)."""
@@ -707,7 +741,10 @@ class _GraphConv(torch.autograd.Function):
         writes the bf16 dX, so g.float(), out.float() and an fp32 [N, F] dX
         never exist.  From PREMASK_ROWS rows one grl_relu_grad_bf16 pass makes
         the masked bf16 gradient, db, and -- only when dW wants it -- the fp32
-        g_eff the dW GEMM reads.  Every gradient is bitwise the widened path's."""
+        g_eff the dW GEMM reads.  Where grl_linear_bwd_weight_bf16g applies
+        (linear_bwd_weight_bf16; from PREMASK_ROWS rows, or without a ReLU) dW
+        reads the masked bf16 gradient too, and no fp32 [N, C] tensor is made
+        at all.  Every gradient is bitwise the widened path's."""
         graph, F = ctx.graph, ctx.xshape[-1]
         g2 = g.reshape(-1, g.shape[-1])
         M, C = g2.shape
@@ -722,21 +759,40 @@ class _GraphConv(torch.autograd.Function):
             return None
         if not (g2.stride(1) == 1 and _rows_apart(g2)):
             g2 = g2.contiguous()
+        # dW from the masked bf16 gradient the dX kernel gathers (grl_linear_bwd_weight_bf16g), where the widened
+        # path's dW is the split-bf16 GEMM on an unmasked operand -- its bits, then, with no fp32 copy of g.  Not
+        # below PREMASK_ROWS with a ReLU: there the widened path's GEMM masks on its loads in the fp32-MFMA
+        # kernel, other bits.  Asked before the mask pass (which then skips its fp32 output) for the tensors as
+        # they will be: the masked gradient and a recomputed Z are new contiguous tensors.
+        gemm = want_w or (want_b and not premask)
+        dw16 = False
+        if gemm and (premask or not relu):
+            K = graph.segments * F
+            g_at, ldg = (_FRESH_ADDRESS, C) if premask else (g2.data_ptr(), _ld(g2))
+            z_at, ldz = (_FRESH_ADDRESS, K) if ctx.recompute else (Z.data_ptr(), _ld(Z))
+            dw16 = _lib.lib().grl_linear_bwd_weight_bf16g_workspace_query(z_at, ldz, g_at, ldg, M, K, C) != 0
         g32 = mask = db_pre = None
         if premask:
-            g16, g32, db_pre = _relu_grad_bf16(g2, out, want_b, want_w)
+            g16, g32, db_pre = _relu_grad_bf16(g2, out, want_b, want_w and not dw16)
         else:
             g16 = torch.where(out > 0, g2, torch.zeros((), dtype=g2.dtype, device=g.device)) if relu else g2
         dX = _bwd_data_run(plan, g16, graph, W, F).view(ctx.xshape)
-        del g16
+        if not dw16:
+            del g16
         dW = db = None
-        if want_w or (want_b and db_pre is None):
-            if not premask:  # the dW GEMM reads fp32 (and masks on its loads below PREMASK_ROWS)
-                g32 = g2.float().contiguous()
-                mask = out.float() if relu else None
+        if gemm:
             if ctx.recompute:
                 Z = spmm_forward(Z, graph)
-            dW, db = linear_bwd_weight(Z, g32, mask, want_b and db_pre is None)
+            res = None
+            if dw16:
+                res = linear_bwd_weight_bf16(Z, g16, want_b and db_pre is None)
+                if res is None:  # (the tensors are not as asked for: the masked gradient widened, the same values)
+                    g32 = g16.float().contiguous()
+                del g16
+            elif not premask:  # the dW GEMM reads fp32 (and masks on its loads below PREMASK_ROWS)
+                g32 = g2.float().contiguous()
+                mask = out.float() if relu else None
+            dW, db = res if res is not None else linear_bwd_weight(Z, g32, mask, want_b and db_pre is None)
         if db_pre is not None:
             db = db_pre
         return dX, None, dW if want_w else None, db, None, None, None
@@ -846,8 +902,10 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
     graphconv_bwd_bf16 path option on) the backward gathers the bf16 gradient
     rows -- half the bytes -- and writes the bf16 X.grad from the kernel's
     epilogue; from PREMASK_ROWS rows one pass (grl_relu_grad_bf16) applies the
-    ReLU mask of the bfloat16 output, sums db and, only if dW is wanted, makes
-    the fp32 gradient the dW GEMM reads.  No g.float(), out.float() or fp32
+    ReLU mask of the bfloat16 output and sums db, and dW reads the masked
+    bfloat16 gradient as stored (grl_linear_bwd_weight_bf16g: a nonzero
+    workspace query, the dw_bf16g path option on; elsewhere the pass also makes
+    the fp32 gradient the dW GEMM reads).  No g.float(), out.float() or fp32
     [N, F] dX exists there.  Elsewhere the backward is the fp32 layer's on
     g.float() with the ReLU mask taken from the bfloat16 output, dX rounded
     once as above.  X.grad, dW and db are the same bits either way.

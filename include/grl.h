@@ -592,6 +592,36 @@ int grl_linear_bwd_weight(const float* Z, int64_t ldz, const float* g,
                           int32_t K, int32_t C, void* workspace,
                           size_t workspace_bytes, grl_stream_t stream);
 
+/* grl_linear_bwd_weight for a g stored as bf16 (bf16 bits, [M, C], rows
+ * ldg >= C elements apart: a column slice of a wider table is a valid g), read
+ * as stored -- no widened copy:
+ *   dW = Z^T g   [K, C] contiguous        db = sum over rows of g   [C] or NULL
+ * Z fp32 [M, K], rows ldz apart.  There is no relu_out: the caller masks first
+ * (grl_relu_grad_bf16's g_eff16).  A bf16 value is ONE plane of the split-bf16
+ * scheme, so the kernel (gemm_x3t_kernel) issues three plane products per
+ * block where grl_linear_bwd_weight's issues six, three of them on planes
+ * that are all zeros; the other three run in the same order over the same K16
+ * steps, splits and slab order, and db is summed in the same row blocks and
+ * order.  dW and db are bitwise grl_linear_bwd_weight(Z, widened g, NULL) for
+ * finite g (-0 included; NaN and Inf are outside the contract).
+ * Eligible -- the query answers grl_linear_bwd_weight_workspace_size(M, K, C),
+ * else 0 -- where grl_linear_bwd_weight would take its split-bf16 kernel
+ * (gemm_x6 on, M >= 16, K % 4 == 0, C % 4 == 0, 2 M K C >= 1.6e10), Z is 16 B-
+ * aligned with ldz % 4 == 0, g is 8 B-aligned with ldg % 4 == 0, and the path
+ * option dw_bf16g is 1.  Anything else: GRL_E_UNSUPPORTED -- there is no
+ * second path inside the library; the caller widens g and runs
+ * grl_linear_bwd_weight.  GRL_E_INVALID, decided on the host: a negative
+ * size, ldz < K, ldg < C, an odd g address, a NULL Z, g or dW with M > 0.  A
+ * missing or short workspace: GRL_E_WORKSPACE.  M == 0 writes dW = 0 and
+ * db = 0; K == 0 or C == 0 returns GRL_OK.  Stream-ordered, no host sync.  */
+size_t grl_linear_bwd_weight_bf16g_workspace_query(const float* Z, int64_t ldz,
+                                                   const uint16_t* g, int64_t ldg,
+                                                   int64_t M, int32_t K, int32_t C);
+int grl_linear_bwd_weight_bf16g(const float* Z, int64_t ldz, const uint16_t* g,
+                                int64_t ldg, float* dW, float* db, int64_t M,
+                                int32_t K, int32_t C, void* workspace,
+                                size_t workspace_bytes, grl_stream_t stream);
+
 /* ReLU's derivative applied once (autograd ThresholdBackward of the ReLU at
  * drop_robust_gcn.py:76, the bias gradient of robust_gcn.py:51 with it):
  *   g_eff = g * [relu_out > 0]  (masked entries +0.0; g_eff may alias g)

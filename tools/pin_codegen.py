@@ -8,6 +8,8 @@ the pinned kernels' instruction streams (comments, directives and label
 names normalised away) and hashes them.  tests/test_codegen_pin.py compares
 the hashes with tests/golden/codegen_pins.json: a mismatch means "re-measure
 the kernel on the GPU and re-pin" (python tools/pin_codegen.py --write).
+KERNELS_DW_BF16G is a second pin set with a file and a test of its own
+(tests/golden/codegen_pins_dw_bf16g.json, tests/test_codegen_pin_dw_bf16g.py).
 
 --all [--root TREE] hashes every kernel of every source in the Makefile's SRCS
 instead, each file with its own flags (the per-object HIPFLAGS additions
@@ -44,6 +46,13 @@ KERNELS = [
     ("graphconv.hip", "_ZN3grl12_GLOBAL__N_119graphconv_ws_kernelILi16ELb0ELb0ELi2ELi4EEE",
      "one-kernel GraphConv forward at F=512, C<=512 (C5 shape: 4 gather + 8 MFMA waves)"),
 ]
+# a pin set of its own (tests/test_codegen_pin_dw_bf16g.py; --write writes it too)
+PINS_DW_BF16G = os.path.join(ROOT, "tests", "golden", "codegen_pins_dw_bf16g.json")
+KERNELS_DW_BF16G = [
+    ("linear.hip", "_ZN3grl12_GLOBAL__N_115gemm_x3t_kernelILi2EEE",
+     "dW from a bf16 gradient, split-K slabs (grl_linear_bwd_weight_bf16g at C3: profiles/"
+     "linear_bwd_weight_bf16g_c3.json)"),
+]
 
 
 def kernel_stream(asm: str, prefix: str):
@@ -66,15 +75,16 @@ def kernel_stream(asm: str, prefix: str):
     return text, sum(1 for t in out if not t.endswith(":"))
 
 
-def compute():
+def compute(kernels=None):
+    kernels = KERNELS if kernels is None else kernels
     res = {}
     with tempfile.TemporaryDirectory() as tmp:
         asm = {}
-        for src in sorted({s for s, _, _ in KERNELS}):
+        for src in sorted({s for s, _, _ in kernels}):
             out = os.path.join(tmp, src + ".s")
             subprocess.run([HIPCC] + FLAGS + [os.path.join(CSRC, src), "-o", out], check=True, capture_output=True)
             asm[src] = open(out).read()
-        for src, prefix, what in KERNELS:
+        for src, prefix, what in kernels:
             text, n = kernel_stream(asm[src], prefix)
             res[prefix] = {"source": src, "what": what, "instructions": n,
                            "sha256": hashlib.sha256(text.encode()).hexdigest()}
@@ -122,9 +132,10 @@ if __name__ == "__main__":
         root = sys.argv[sys.argv.index("--root") + 1] if "--root" in sys.argv else ROOT
         print(json.dumps(compute_all(os.path.abspath(root)), indent=1, sort_keys=True))
         sys.exit(0)
-    pins = compute()
-    if "--write" in sys.argv:
-        with open(PINS, "w") as f:
-            json.dump(pins, f, indent=1)
-            f.write("\n")
-    print(json.dumps(pins, indent=1))
+    for path, kernels in ((PINS, KERNELS), (PINS_DW_BF16G, KERNELS_DW_BF16G)):
+        pins = compute(kernels)
+        if "--write" in sys.argv:
+            with open(path, "w") as f:
+                json.dump(pins, f, indent=1)
+                f.write("\n")
+        print(json.dumps(pins, indent=1))
