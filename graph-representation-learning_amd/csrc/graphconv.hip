@@ -547,12 +547,7 @@ __global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_bf16_kernel(
 #define GRL_WS_OUT16_PACK 1
 #endif
 
-// two fp32 -> one dword of two bf16 (lo in bits 15:0), each rounded to nearest even
-__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
-  uint32_t r;
-  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
+// (cvt_pk_bf16, the rounding of the epilogue's stores: grl_internal.h)
 // lane l ^ 1's value (a DPP move within the quad, no LDS)
 __device__ __forceinline__ float swap_lane_pair(float v) {
   return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));  // quad_perm [1, 0, 3, 2]

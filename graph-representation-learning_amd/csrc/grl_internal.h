@@ -139,6 +139,14 @@ __device__ __forceinline__ float readlane_f(float v, int lane) {
 }
 __device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// two fp32 -> one dword of two bf16 (lo in bits 15:0), each rounded to nearest even: the library's one
+// fp32 -> bf16 rounding (the bf16-output GraphConv epilogue, the bf16 feature dropout, the scaled ReLU mask pass)
+__device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
+  uint32_t r;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
+  return r;
+}
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // roctx range around a C-ABI entry point: `rocprofv3 --marker-trace` shows

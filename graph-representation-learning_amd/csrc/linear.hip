@@ -470,6 +470,49 @@ __global__ __launch_bounds__(256) void relu_grad_bf16_colsum_kernel(const uint16
   if (partial) partial[z * C + c] = s;
 }
 
+// relu_grad_bf16_colsum_kernel with a scale (grl_relu_grad_bf16_scaled: the
+// backward of feature dropout + ReLU over the saved dropped output): x =
+// relu_out > 0 ? RNE_bf16(float(g) * scale) : +0, one rounding (cvt_pk_bf16,
+// the bf16-output epilogue's).  The same operands, NULL-able outputs, row
+// blocks and summing order over the widened x.
+__global__ __launch_bounds__(256) void relu_grad_bf16_scaled_colsum_kernel(
+    const uint16_t* g, int64_t ldg, const uint16_t* __restrict__ relu_out, int64_t ldo, uint16_t* g_eff16, int64_t lde,
+    float* __restrict__ g_eff32, int64_t M, int64_t C, int64_t rows_per, float scale, float* __restrict__ partial) {
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t z = blockIdx.y;
+  if (c >= C) return;
+  const int64_t r0 = z * rows_per, r1 = min(M, r0 + rows_per);
+  auto widen = [](uint16_t h) { return __uint_as_float((uint32_t)h << 16); };
+  float s = 0.0f;
+  int64_t r = r0;
+  for (; r + 8 <= r1; r += 8) {
+    uint16_t b[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const uint16_t v = (uint16_t)cvt_pk_bf16(widen(g[(r + u) * ldg + c]) * scale, 0.0f);
+      b[u] = widen(relu_out[(r + u) * ldo + c]) > 0.0f ? v : (uint16_t)0;
+    }
+    if (g_eff16) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) g_eff16[(r + u) * lde + c] = b[u];
+    }
+    if (g_eff32) {
+#pragma unroll
+      for (int u = 0; u < 8; ++u) g_eff32[(r + u) * C + c] = widen(b[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) s += widen(b[u]);
+  }
+  for (; r < r1; ++r) {
+    const uint16_t v = (uint16_t)cvt_pk_bf16(widen(g[r * ldg + c]) * scale, 0.0f);
+    const uint16_t b = widen(relu_out[r * ldo + c]) > 0.0f ? v : (uint16_t)0;
+    if (g_eff16) g_eff16[r * lde + c] = b;
+    if (g_eff32) g_eff32[r * C + c] = widen(b);
+    s += widen(b);
+  }
+  if (partial) partial[z * C + c] = s;
+}
+
 // colsum_partial_kernel over bf16 bits with rows ldg apart and no mask
 // (grl_linear_bwd_weight_bf16g's db): the same row blocks, each value widened
 // (exact) and added in the same order, so db is bitwise that kernel's on the
@@ -1572,34 +1615,39 @@ extern "C" int grl_relu_grad(const float* g, const float* relu_out, float* g_eff
   return GRL_OK;
 }
 
-extern "C" int grl_relu_grad_bf16(const uint16_t* g, int64_t ldg, const uint16_t* relu_out, int64_t ldo,
-                                  uint16_t* g_eff16, int64_t lde, float* g_eff32, float* db, int64_t M, int32_t C,
-                                  void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+// grl_relu_grad_bf16 and grl_relu_grad_bf16_scaled (scale != NULL): one host path, two kernels
+static int relu_grad_bf16_run(const char* who, const uint16_t* g, int64_t ldg, const uint16_t* relu_out, int64_t ldo,
+                              uint16_t* g_eff16, int64_t lde, float* g_eff32, float* db, int64_t M, int32_t C,
+                              const float* scale, void* workspace, size_t workspace_bytes, grl_stream_t stream) {
   using namespace grl;
-  TraceRange trace_("grl_relu_grad_bf16");
-  GRL_CHECK_ARG(M >= 0 && C >= 0, "grl_relu_grad_bf16: bad sizes");
+  GRL_CHECK_ARG(M >= 0 && C >= 0, "%s: bad sizes", who);
   if (C == 0) return GRL_OK;
   if (M == 0) {  // no rows (an empty node-range shard): nothing to mask, db = 0
     if (db && hipMemsetAsync(db, 0, (size_t)C * sizeof(float), as_stream(stream)) != hipSuccess)
-      GRL_FAIL(GRL_E_HIP, "grl_relu_grad_bf16: hipMemsetAsync failed");
+      GRL_FAIL(GRL_E_HIP, "%s: hipMemsetAsync failed", who);
     return GRL_OK;
   }
-  GRL_CHECK_ARG(g && relu_out, "grl_relu_grad_bf16: NULL pointer");
+  GRL_CHECK_ARG(g && relu_out, "%s: NULL pointer", who);
   GRL_CHECK_ARG(ldg >= C && ldo >= C && (!g_eff16 || lde >= C),
-                "grl_relu_grad_bf16: need ldg, ldo and lde >= C (ldg=%lld ldo=%lld lde=%lld C=%d)", (long long)ldg,
+                "%s: need ldg, ldo and lde >= C (ldg=%lld ldo=%lld lde=%lld C=%d)", who, (long long)ldg,
                 (long long)ldo, (long long)lde, C);
   GRL_CHECK_ARG((reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(relu_out) |
                  reinterpret_cast<uintptr_t>(g_eff16)) % 2 == 0 && reinterpret_cast<uintptr_t>(g_eff32) % 4 == 0,
-                "grl_relu_grad_bf16: g, relu_out and g_eff16 must be 2-B aligned, g_eff32 4-B aligned");
+                "%s: g, relu_out and g_eff16 must be 2-B aligned, g_eff32 4-B aligned", who);
   const size_t need = grl_relu_grad_workspace_size(M, C);
   if (db && (!workspace || workspace_bytes < need))
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_relu_grad_bf16: workspace %zu < %zu", workspace_bytes, need);
+    GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
   hipStream_t st = as_stream(stream);
   const int zs = colsum_splits(M);
   const int64_t rows_per = ceil_div(std::max<int64_t>(M, 1), zs);
   float* part = db ? static_cast<float*>(workspace) : nullptr;
-  hipLaunchKernelGGL(relu_grad_bf16_colsum_kernel, dim3((unsigned)ceil_div(C, 256), (unsigned)zs), dim3(256), 0, st, g,
-                     ldg, relu_out, ldo, g_eff16, lde, g_eff32, M, (int64_t)C, rows_per, part);
+  const dim3 grid((unsigned)ceil_div(C, 256), (unsigned)zs);
+  if (scale)
+    hipLaunchKernelGGL(relu_grad_bf16_scaled_colsum_kernel, grid, dim3(256), 0, st, g, ldg, relu_out, ldo, g_eff16, lde,
+                       g_eff32, M, (int64_t)C, rows_per, *scale, part);
+  else
+    hipLaunchKernelGGL(relu_grad_bf16_colsum_kernel, grid, dim3(256), 0, st, g, ldg, relu_out, ldo, g_eff16, lde,
+                       g_eff32, M, (int64_t)C, rows_per, part);
   GRL_LAUNCH_CHECK();
   if (db) {
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs,
@@ -1607,6 +1655,23 @@ extern "C" int grl_relu_grad_bf16(const uint16_t* g, int64_t ldg, const uint16_t
     GRL_LAUNCH_CHECK();
   }
   return GRL_OK;
+}
+
+extern "C" int grl_relu_grad_bf16(const uint16_t* g, int64_t ldg, const uint16_t* relu_out, int64_t ldo,
+                                  uint16_t* g_eff16, int64_t lde, float* g_eff32, float* db, int64_t M, int32_t C,
+                                  void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  grl::TraceRange trace_("grl_relu_grad_bf16");
+  return relu_grad_bf16_run("grl_relu_grad_bf16", g, ldg, relu_out, ldo, g_eff16, lde, g_eff32, db, M, C, nullptr,
+                            workspace, workspace_bytes, stream);
+}
+
+extern "C" int grl_relu_grad_bf16_scaled(const uint16_t* g, int64_t ldg, const uint16_t* relu_out, int64_t ldo,
+                                         uint16_t* g_eff16, int64_t lde, float* g_eff32, float* db, int64_t M,
+                                         int32_t C, float scale, void* workspace, size_t workspace_bytes,
+                                         grl_stream_t stream) {
+  grl::TraceRange trace_("grl_relu_grad_bf16_scaled");
+  return relu_grad_bf16_run("grl_relu_grad_bf16_scaled", g, ldg, relu_out, ldo, g_eff16, lde, g_eff32, db, M, C,
+                            &scale, workspace, workspace_bytes, stream);
 }
 
 extern "C" int grl_linear_bwd_weight(const float* Z, int64_t ldz, const float* g, const float* relu_out, float* dW,

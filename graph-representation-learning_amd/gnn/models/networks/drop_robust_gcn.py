@@ -174,6 +174,8 @@ class FeatureDropout(nn.Dropout):
             return x
         if not x.is_cuda or not self._hash:
             return super().forward(x)
+        if x.dtype == torch.bfloat16:  # read and written as stored (grl_feature_dropout_bf16): no widened copy
+            return feature_dropout(x, self.record(x.device), self.row0)
         return feature_dropout(x.float(), self.record(x.device), self.row0)
 
 
@@ -192,9 +194,24 @@ class GraphCNNDropEdge(BaseNetwork):
     cat[g1, g3].float(), and everything after it is fp32 as ever.  It applies
     in eval mode with gradients disabled (torch.no_grad) on an unsharded
     TypedGraph on the GPU.  In every other situation -- training mode
-    (feature dropout and the gradient kernels are fp32), gradients enabled, a
+    (train_activation_dtype below is the switch there), gradients enabled, a
     node-range shard, a dense A, the CPU, the default None -- the attribute is
-    ignored and the fp32 path runs, bit for bit as without it."""
+    ignored and the fp32 path runs, bit for bit as without it.
+
+    `train_activation_dtype` (likewise an attribute; default None) is the
+    training-mode counterpart: with torch.bfloat16, in training mode on an
+    unsharded TypedGraph on the GPU, the embedding is cast once and dropped as
+    bfloat16 (grl_feature_dropout_bf16), and the three GraphConv layers run
+    with a bfloat16 table, a bfloat16 output and their feature dropout fused
+    into the layer's autograd node (grl.ops.graph_conv(..., fdrop=)): gcn2
+    reads g1, gcn3 reads cat[g1, g2] (torch.cat on bfloat16), and the gradients
+    between the layers are bfloat16 -- the one-kernel data gradient gathers
+    them as stored, dW reads them as stored.  emb2 takes cat[g1, g3].float();
+    everything from there on is fp32 as ever, and so are all parameters and
+    their gradients.  The feature masks are those of the fp32 model (the same
+    element ids and hash).  Everywhere else -- eval mode, a node-range shard, a
+    dense A, the CPU, the default None -- this attribute is ignored and today's
+    path runs bit for bit."""
 
     def __init__(self, input_dim: int, output_dim: int, num_edges: int, net_size: int = 256,
                  use_attention: bool = True, dropedge_seed: Optional[int] = None):
@@ -207,6 +224,8 @@ class GraphCNNDropEdge(BaseNetwork):
         self.sparse_emb1 = True
         # torch.bfloat16: the GraphConv activations of an eval forward in one bf16 table (class docstring)
         self.activation_dtype: Optional[torch.dtype] = None
+        # torch.bfloat16: the GraphConv activations and the gradients between them bf16 in training (class docstring)
+        self.train_activation_dtype: Optional[torch.dtype] = None
         self.dropout = FeatureDropout(p=0.5, seed=dropedge_seed)
         self.edge_dropout = EdgeDropout(p=0.3, seed=dropedge_seed)
         self.gcn1 = GraphConv(self.net_size, self.net_size, num_edges)
@@ -255,6 +274,9 @@ class GraphCNNDropEdge(BaseNetwork):
         if (self.activation_dtype == torch.bfloat16 and not self.training and not torch.is_grad_enabled()
                 and isinstance(A, TypedGraph) and V.is_cuda):
             return self._head(self._gcn_bf16(V, graph, bool(efficient_mode)), graph, False, pr)
+        if (self.train_activation_dtype == torch.bfloat16 and self.training and isinstance(A, TypedGraph)
+                and V.is_cuda):
+            return self._head(self._gcn_bf16_train(V, graph, bool(efficient_mode)), graph, False, pr)
         embedding = self.dropout(self._embed(V))
         # efficient_mode=True: dropout covers the identity block of A_pre
         # (:69,:76); False: dropout hits raw A, identity added after (:72-74).
@@ -289,6 +311,22 @@ class GraphCNNDropEdge(BaseNetwork):
         g1 = self.gcn1.propagate(x0, self.edge_dropout(graph, ds), relu=True, out=table[:, :C])
         self.gcn2.propagate(g1, self.edge_dropout(graph, ds), relu=True, out=table[:, C:])
         g3 = self.gcn3.propagate(table, self.edge_dropout(graph, ds), relu=True, out_dtype=torch.bfloat16)
+        return torch.cat([g1, g3], dim=-1).float().view(*lead, 2 * C)
+
+    def _gcn_bf16_train(self, V: torch.Tensor, graph: TypedGraph, ds: bool) -> torch.Tensor:
+        """emb1 and the three GraphConv layers of a training forward with
+        bfloat16 activations (train_activation_dtype): each layer one autograd
+        node with its ReLU and feature dropout, the gradients between them
+        bfloat16; emb2's fp32 input cat[g1, g3]."""
+        C = self.net_size
+        emb = self._embed(V)
+        lead = emb.shape[:-1]
+        bf16 = torch.bfloat16
+        x0 = self.dropout(emb.reshape(-1, C).to(bf16))  # the one cast, then the bf16 dropout (:64)
+        g1 = self.gcn1.propagate(x0, self.edge_dropout(graph, ds), relu=True, dropout=self.dropout, out_dtype=bf16)
+        g2 = self.gcn2.propagate(g1, self.edge_dropout(graph, ds), relu=True, dropout=self.dropout, out_dtype=bf16)
+        g3 = self.gcn3.propagate(torch.cat([g1, g2], dim=-1), self.edge_dropout(graph, ds), relu=True,
+                                 dropout=self.dropout, out_dtype=bf16)
         return torch.cat([g1, g3], dim=-1).float().view(*lead, 2 * C)
 
     def _head(self, x: torch.Tensor, graph, sharded: bool, pr: int) -> torch.Tensor:

@@ -141,6 +141,14 @@ class GraphConv(nn.Module):
                 out = dropout(out) if dropout is not None else out
             return out.view(*lead, self.C)
         # new_V = A_pre V (B*N, (L+1)F) then new_V h_weights + bias, one autograd node
+        if out_dtype == torch.bfloat16 and hasattr(dropout, "record") and getattr(dropout, "_hash", True):
+            # a bf16 output under a hash-mask dropout: the record rides into the node (graph_conv's fdrop: with a
+            # ReLU the dropout runs in place on the layer's output and the backward is one scaled mask pass)
+            fd = dropout.record(V.device)
+            if fd is not None:
+                out = graph_conv(V, graph, self.h_weights, self.bias, relu=relu, recompute=self.recompute_aggregation,
+                                 out_dtype=out_dtype, fdrop=fd, row0=getattr(dropout, "row0", 0))
+                return out.view(*lead, self.C)
         out = graph_conv(V, graph, self.h_weights, self.bias, relu=relu, recompute=self.recompute_aggregation,
                          out_dtype=out_dtype)
         out = out.view(*lead, self.C)

@@ -136,6 +136,8 @@ SIGNATURES = {
     "grl_dropedge_init_device": (_c_i32, [_P(GrlDropEdge), ctypes.c_float, _c_vp, _c_u64, _c_i32]),
     "grl_dropedge_mask": (_c_i32, [_P(GrlDropEdge), _c_u64, _c_i64, _c_vp, _c_vp]),
     "grl_feature_dropout": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i64, _P(GrlDropEdge), _c_vp]),
+    "grl_feature_dropout_bf16": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i64, _P(GrlDropEdge),
+                                          _c_vp]),
     "grl_typed_spmm_fwd": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_fwd_slice": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_i64, _c_vp, _c_i64, _c_i32,
                                           _P(GrlDropEdge), _c_vp]),
@@ -185,6 +187,8 @@ SIGNATURES = {
     "grl_relu_grad": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp, _c_size, _c_vp]),
     "grl_relu_grad_bf16": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i32, _c_vp,
                                     _c_size, _c_vp]),
+    "grl_relu_grad_bf16_scaled": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i32,
+                                           ctypes.c_float, _c_vp, _c_size, _c_vp]),
     "grl_linear_bwd_weight_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32]),
     "grl_linear_bwd_weight": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp,
                                        _c_size, _c_vp]),

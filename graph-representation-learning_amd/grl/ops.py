@@ -291,10 +291,20 @@ def relu_grad_bf16(g: torch.Tensor, out: torch.Tensor, want_db: bool = False, wa
     return _relu_grad_bf16(g, out, want_db, want_f32)
 
 
-def _relu_grad_bf16(g, out, want_db, want_f32, g_eff16=None, want_16=True):
+def relu_grad_bf16_scaled(g: torch.Tensor, out: torch.Tensor, scale: float, want_db: bool = False,
+                          want_f32: bool = False):
+    """relu_grad_bf16 with a scale (grl_relu_grad_bf16_scaled): x = out > 0 ?
+    RNE_bf16(float(g) * scale) : +0 -- the backward of ReLU then feature
+    dropout in one pass when `out` is the DROPPED output (> 0 exactly where the
+    element was kept and the ReLU open) and scale the record's 1 / (1 - p).
+    (g_eff16, g_eff32, db) as there, over x."""
+    return _relu_grad_bf16(g, out, want_db, want_f32, scale=scale)
+
+
+def _relu_grad_bf16(g, out, want_db, want_f32, g_eff16=None, want_16=True, scale=None):
     """relu_grad_bf16 with the C entry's other forms: `g_eff16` names the
-    tensor to write (strided; g itself masks in place) and want_16=False skips
-    that output."""
+    tensor to write (strided; g itself masks in place), want_16=False skips
+    that output and `scale` takes grl_relu_grad_bf16_scaled."""
     _require_device(g, "relu_grad_bf16 g")
     tensors = [g, out] + ([g_eff16] if g_eff16 is not None else [])
     if any(t.dtype != torch.bfloat16 or t.dim() != 2 or t.shape != g.shape or (t.shape[1] > 0 and t.stride(1) != 1)
@@ -311,9 +321,9 @@ def _relu_grad_bf16(g, out, want_db, want_f32, g_eff16=None, want_16=True):
     db = torch.empty(C, dtype=torch.float32, device=g.device) if want_db else None
     ws_bytes = _lib.lib().grl_relu_grad_workspace_size(M, C) if want_db else 0
     ws = _workspace(ws_bytes, g.device)
-    call("grl_relu_grad_bf16", g.data_ptr(), _ld(g), out.data_ptr(), _ld(out), _ptr(g_eff16),
-         _ld(g_eff16) if g_eff16 is not None else 0, _ptr(g_eff32), _ptr(db), M, C, _ptr(ws), ws_bytes,
-         current_stream_handle(g.device))
+    call("grl_relu_grad_bf16" if scale is None else "grl_relu_grad_bf16_scaled", g.data_ptr(), _ld(g), out.data_ptr(),
+         _ld(out), _ptr(g_eff16), _ld(g_eff16) if g_eff16 is not None else 0, _ptr(g_eff32), _ptr(db), M, C,
+         *([] if scale is None else [float(scale)]), _ptr(ws), ws_bytes, current_stream_handle(g.device))
     return g_eff16, g_eff32, db
 
 
@@ -663,13 +673,16 @@ class _GraphConv(torch.autograd.Function):
     Z and output gradient, dX rounded once to X's dtype -- and with a bf16
     output gradient too, where grl_graphconv_bwd_data_bf16 applies, the data
     gradient gathers that gradient as stored and writes the bf16 dX itself,
-    the same bits with no widened copy: _backward_bf16).  (Running dW on a second HIP
+    the same bits with no widened copy: _backward_bf16).  fdrop (with a ReLU
+    and a bf16 output): the feature dropout that follows the layer, applied
+    in place to the output in the forward and as one scaled mask pass over the
+    saved dropped output in the backward (graph_conv).  (Running dW on a second HIP
     stream beside dZ / the transposed gather was measured and bought nothing:
     39-41 ms per C3 layer either way, each kernel already fills the chip.)"""
 
     @staticmethod
     def forward(ctx, X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b, relu: bool, recompute: bool,
-                out_bf16: bool = False):
+                out_bf16: bool = False, fdrop=None, row0: int = 0):
         Wc = W.contiguous()
         bc = b.contiguous() if b is not None else None
         # out_bf16 (a bf16 X on a TypedGraph: graph_conv checks): the layer's epilogue writes bf16
@@ -684,6 +697,13 @@ class _GraphConv(torch.autograd.Function):
             out, Z = graph_conv_fwd_train(X, graph, Wc, bc, relu, out=out)
         ctx.graph, ctx.relu, ctx.has_b, ctx.xshape, ctx.xdtype = graph, relu, b is not None, X.shape, X.dtype
         ctx.recompute = recompute
+        # fdrop (relu and out_bf16: graph_conv checks): the feature dropout in place on the fresh bf16 output, which
+        # is then the one tensor returned and saved -- > 0 exactly where kept and open, so the backward needs the
+        # record's scale alone (grl_relu_grad_bf16_scaled), no hash and no pre-dropout copy
+        ctx.fscale = None
+        if fdrop is not None:
+            feature_dropout_apply(out, fdrop, row0, out=out)
+            ctx.fscale = float(fdrop.to_c().scale)
         # recompute: keep X (F wide) instead of Z ((L+1)F wide); the backward
         # regenerates Z with the same DropEdge record, so it is the same bits
         ctx.save_for_backward(X if recompute else Z, Wc, out if relu else None)
@@ -699,6 +719,14 @@ class _GraphConv(torch.autograd.Function):
             res = _GraphConv._backward_bf16(ctx, g, Z, W, out, want_w, want_b)
             if res is not None:
                 return res
+        if ctx.fscale is not None:
+            # the fused dropout where the bf16 data gradient does not apply: the masked, scaled bf16 gradient
+            # first (one pass over g and the dropped output), then the widened path on it -- whose own mask
+            # [out > 0] selects what is already selected
+            g2 = g.reshape(-1, g.shape[-1])
+            if not (g2.stride(1) == 1 and _rows_apart(g2)):
+                g2 = g2.contiguous()
+            g = _relu_grad_bf16(g2, out, False, False, scale=ctx.fscale)[0]
         # a bf16 out hands back a bf16 g: the fp32 layer's backward on g.float(), the ReLU mask from the bf16
         # out ([out > 0] survives the rounding); both widened to fp32 here
         g, mask, db_pre = relu_grad(g.contiguous().float(), out.float() if ctx.relu else None, want_b)
@@ -715,7 +743,7 @@ class _GraphConv(torch.autograd.Function):
                 del G_agg
                 dW = dWt.view(F, S, C).transpose(0, 1).reshape(S * F, C)
                 db = (db_pre if db_pre is not None else g_eff.sum(0)) if want_b else None
-                return dX.view(ctx.xshape), None, dW, db, None, None, None
+                return dX.view(ctx.xshape), None, dW, db, None, None, None, None, None
         if ctx.recompute and (want_w or (want_b and db_pre is None)):
             Z = spmm_forward(Z, ctx.graph)
         dW = db = dX = None
@@ -731,7 +759,7 @@ class _GraphConv(torch.autograd.Function):
             dW, db = linear_bwd_weight(Z, g, mask, want_b and db_pre is None)
         if db_pre is not None:
             db = db_pre
-        return dX, None, dW if want_w else None, db, None, None, None
+        return dX, None, dW if want_w else None, db, None, None, None, None, None
 
     @staticmethod
     def _backward_bf16(ctx, g: torch.Tensor, Z, W: torch.Tensor, out, want_w: bool, want_b: bool):
@@ -773,7 +801,12 @@ class _GraphConv(torch.autograd.Function):
             dw16 = _lib.lib().grl_linear_bwd_weight_bf16g_workspace_query(z_at, ldz, g_at, ldg, M, K, C) != 0
         g32 = mask = db_pre = None
         if premask:
-            g16, g32, db_pre = _relu_grad_bf16(g2, out, want_b, want_w and not dw16)
+            g16, g32, db_pre = _relu_grad_bf16(g2, out, want_b, want_w and not dw16, scale=ctx.fscale)
+        elif ctx.fscale is not None:
+            # the fused dropout below PREMASK_ROWS: the scaled pass still makes the gradient (masked by the dropped
+            # output, scaled, rounded once) and its fp32 copy for the dW GEMM, which keeps masking on its loads
+            # with the dropped output -- it selects the same values as the unfused chain's, so the same bits
+            g16, g32, _ = _relu_grad_bf16(g2, out, False, gemm, scale=ctx.fscale)
         else:
             g16 = torch.where(out > 0, g2, torch.zeros((), dtype=g2.dtype, device=g.device)) if relu else g2
         dX = _bwd_data_run(plan, g16, graph, W, F).view(ctx.xshape)
@@ -790,12 +823,12 @@ class _GraphConv(torch.autograd.Function):
                     g32 = g16.float().contiguous()
                 del g16
             elif not premask:  # the dW GEMM reads fp32 (and masks on its loads below PREMASK_ROWS)
-                g32 = g2.float().contiguous()
+                g32 = g2.float().contiguous() if ctx.fscale is None else g32
                 mask = out.float() if relu else None
             dW, db = res if res is not None else linear_bwd_weight(Z, g32, mask, want_b and db_pre is None)
         if db_pre is not None:
             db = db_pre
-        return dX, None, dW if want_w else None, db, None, None, None
+        return dX, None, dW if want_w else None, db, None, None, None, None, None
 
 
 def graph_conv_fwd_train(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu: bool = False,
@@ -868,7 +901,7 @@ RECOMPUTE_Z_BYTES = 8 << 30
 
 
 def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu: bool = False,
-               recompute: bool = None, out_dtype=None) -> torch.Tensor:
+               recompute: bool = None, out_dtype=None, fdrop=None, row0: int = 0) -> torch.Tensor:
     """GraphConv forward (aggregation + linear [+ReLU]) as one autograd node;
     X: [num_cols, F] (or [B, N, F] for a batch graph).  When no gradient is
     wanted (eval, torch.no_grad) it is one grl_graphconv_fwd call instead:
@@ -909,7 +942,23 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
     [N, F] dX exists there.  Elsewhere the backward is the fp32 layer's on
     g.float() with the ReLU mask taken from the bfloat16 output, dX rounded
     once as above.  X.grad, dW and db are the same bits either way.
-    recompute=True keeps the bf16 X and re-aggregates Z, as above."""
+    recompute=True keeps the bf16 X and re-aggregates Z, as above.
+    fdrop (a DropEdge record, as FeatureDropout.record() returns; row0 the
+    global row of the first output row): the feature dropout that follows the
+    layer, feature_dropout(out, fdrop, row0).  With relu=True and
+    out_dtype=torch.bfloat16 it is fused into the node: the forward runs
+    grl_feature_dropout_bf16 IN PLACE on the layer's fresh bfloat16 output and
+    returns and saves that one tensor (no pre-dropout copy is kept), and the
+    backward makes the masked, scaled bfloat16 gradient in one
+    grl_relu_grad_bf16_scaled pass at every row count (the dropped output is
+    > 0 exactly where the element was kept and the ReLU open, so one selection
+    is both masks and no hash is drawn); below PREMASK_ROWS the dW GEMM stays
+    the one that masks on its loads, reading that gradient widened with the
+    dropped output as its mask.  out, X.grad, dW and db are bitwise those of
+    the unfused chain feature_dropout(graph_conv(...), fdrop, row0).  With
+    gradients disabled it is graph_conv_infer followed by the in-place pass.
+    In every other combination (an fp32 output, no ReLU, an EdgeBlockedGraph)
+    fdrop is applied as a separate feature_dropout after the node."""
     if X.dtype not in _TABLE_DTYPES:
         raise _lib.GrlError(f"graph_conv: node features must be float32 or bfloat16 (got {X.dtype})")
     if W.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
@@ -920,15 +969,20 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
     if out_bf16 and (X.dtype != torch.bfloat16 or isinstance(graph, EdgeBlockedGraph)):
         raise _lib.GrlError(f"graph_conv: out_dtype=bfloat16 needs bfloat16 node features on a TypedGraph (got "
                             f"{X.dtype}): there is no fp32-table form with a bf16 output -- cast the table once")
+    fused = fdrop is not None and relu and out_bf16
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (X, W, b))):
         if isinstance(graph, EdgeBlockedGraph):  # one int32 CSR per call: aggregate by blocks, then the linear
-            return linear_fwd(spmm_forward(X, graph), W.contiguous(), b.contiguous() if b is not None else None,
-                              relu)
-        out = torch.empty(graph.num_rows, W.shape[1], dtype=torch.bfloat16, device=X.device) if out_bf16 else None
-        return graph_conv_infer(X, graph, W, b, relu, out=out)
+            out = linear_fwd(spmm_forward(X, graph), W.contiguous(), b.contiguous() if b is not None else None, relu)
+        else:
+            out = torch.empty(graph.num_rows, W.shape[1], dtype=torch.bfloat16, device=X.device) if out_bf16 else None
+            out = graph_conv_infer(X, graph, W, b, relu, out=out)
+        if fused:
+            return feature_dropout_apply(out, fdrop, int(row0), out=out)
+        return out if fdrop is None else feature_dropout(out, fdrop, row0)
     if recompute is None:
         recompute = graph.num_rows * graph.segments * X.shape[-1] * 4 > RECOMPUTE_Z_BYTES
-    return _GraphConv.apply(X, graph, W, b, relu, bool(recompute), out_bf16)
+    out = _GraphConv.apply(X, graph, W, b, relu, bool(recompute), out_bf16, fdrop if fused else None, int(row0))
+    return out if fused or fdrop is None else feature_dropout(out, fdrop, row0)
 
 
 def graph_linear(Z: torch.Tensor, W: torch.Tensor, b=None, relu: bool = False, path_rows: int = 0) -> torch.Tensor:
@@ -941,12 +995,32 @@ def graph_linear(Z: torch.Tensor, W: torch.Tensor, b=None, relu: bool = False, p
 
 
 # -------------------------------------------------------- feature dropout
+def _bf16_rows(t: torch.Tensor) -> bool:
+    """A 2-D bfloat16 tensor with unit column stride and its rows apart (a
+    column-slice view of a wider table included)."""
+    return (t.dtype == torch.bfloat16 and t.dim() == 2 and (t.shape[1] == 0 or t.stride(1) == 1) and _rows_apart(t))
+
+
 def feature_dropout_apply(x2: torch.Tensor, de, row0: int, out: torch.Tensor = None) -> torch.Tensor:
     """out = x2 * keep * 1/(1-p) for the element ids (row0 + r) * cols + c
-    (grl_feature_dropout); x2 a 2-D fp32 row view."""
+    (grl_feature_dropout); x2 a 2-D fp32 row view.  Or a 2-D bfloat16 tensor
+    with unit column stride and its rows apart, read as stored
+    (grl_feature_dropout_bf16: bitwise the fp32 result on x2.float(), rounded
+    once to nearest even; no widened copy): `out` is then a bfloat16 tensor of
+    the same kind and shape, x2 itself included (the pass runs in place)."""
     _require_device(x2, "dropout input")
+    if x2.dtype == torch.bfloat16:
+        if out is None:
+            out = torch.empty(x2.shape, dtype=torch.bfloat16, device=x2.device)
+        if not _bf16_rows(x2) or not _bf16_rows(out) or out.shape != x2.shape or out.device != x2.device:
+            raise _lib.GrlError("feature_dropout: a bfloat16 input and out must be 2-D bfloat16 tensors of one shape on "
+                                "one device with unit column stride and a row stride of at least their width")
+        dc = de.to_c()
+        call("grl_feature_dropout_bf16", x2.data_ptr(), _ld(x2), out.data_ptr(), _ld(out), x2.shape[0], x2.shape[1],
+             int(row0), ctypes.byref(dc), current_stream_handle(x2.device))
+        return out
     if x2.dtype != torch.float32 or x2.dim() != 2 or x2.stride(1) != 1:
-        raise _lib.GrlError("feature_dropout: a 2-D float32 tensor with unit column stride")
+        raise _lib.GrlError("feature_dropout: a 2-D float32 (or bfloat16) tensor with unit column stride")
     if out is None:
         out = torch.empty(x2.shape, dtype=torch.float32, device=x2.device)
     dc = de.to_c()
@@ -963,6 +1037,7 @@ class _FeatureDropout(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
+        # (a bfloat16 gradient goes through the bf16 entry as stored: the same map, no widened copy)
         return feature_dropout_apply(_rows_view(g.contiguous()), ctx.de, ctx.row0), None, None
 
 
@@ -971,7 +1046,9 @@ def feature_dropout(x: torch.Tensor, de, row0: int = 0) -> torch.Tensor:
     row, column) a counter hash under the DropEdge record `de` (its p, seed
     / seed tensor and call id): drop_robust_gcn.py:64,77,81,86,100.  row0:
     the global row of x's first row (a node-range shard's row_begin), so a
-    shard's rows get the one-GPU model's mask."""
+    shard's rows get the one-GPU model's mask.  x float32, or bfloat16 read
+    as stored (feature_dropout_apply): the result and the gradient are then
+    bfloat16, each the fp32 map's value rounded once."""
     lead = x.shape[:-1]
     x2 = _rows_view(x)
     return _FeatureDropout.apply(x2, de, int(row0)).view(*lead, x.shape[-1])

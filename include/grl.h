@@ -222,6 +222,23 @@ int grl_feature_dropout(const float* x, int64_t ldx, float* out, int64_t ldo,
                         int64_t rows, int32_t cols, int64_t row0,
                         const GrlDropEdge* de, grl_stream_t stream);
 
+/* grl_feature_dropout over bf16 bits: the same element ids, hash and keep
+ * rule, so a column slice of a table with cols = C draws exactly the fp32
+ * model's mask for that layer.  out is bitwise grl_feature_dropout on the
+ * widened x, rounded once to nearest even: a kept element is
+ * RNE_bf16(float(x) * scale), a dropped one bf16 +0, and an inactive record
+ * copies the bits.  x / out: rows ldx / ldo >= cols ELEMENTS apart (a column
+ * slice of a wider table is a valid operand), 2-B aligned; out may alias x
+ * (the pass runs in place).  16 B per lane where both pointers are 16-B
+ * aligned and cols, ldx, ldo are multiples of 8, 8 B on the matching 8-B /
+ * multiple-of-4 conditions, else one element per lane -- the same bits.
+ * Errors as grl_feature_dropout; an odd address is GRL_E_INVALID.  No host
+ * sync.                                                                    */
+int grl_feature_dropout_bf16(const uint16_t* x, int64_t ldx, uint16_t* out,
+                             int64_t ldo, int64_t rows, int32_t cols,
+                             int64_t row0, const GrlDropEdge* de,
+                             grl_stream_t stream);
+
 /* keep[i] = 1 if id_base + i survives DropEdge `de`, else 0 (i < count).
  * Exposes the fused mask for parity checks against the dense reference
  * (the mask nn.Dropout would draw over A_pre, drop_robust_gcn.py:76).    */
@@ -651,6 +668,24 @@ int grl_relu_grad_bf16(const uint16_t* g, int64_t ldg, const uint16_t* relu_out,
                        float* g_eff32, float* db, int64_t M, int32_t C,
                        void* workspace, size_t workspace_bytes,
                        grl_stream_t stream);
+
+/* grl_relu_grad_bf16 with a scale -- the backward of ReLU followed by feature
+ * dropout in one pass, when relu_out is the DROPPED output
+ * (grl_feature_dropout_bf16 applied in place to the layer's bf16 output):
+ *   x = relu_out > 0 ? RNE_bf16(float(g) * scale) : +0
+ * with scale the record's 1 / (1 - p).  The dropped output is > 0 exactly
+ * where the element was kept and the ReLU was open (a positive bf16 times
+ * scale >= 1 never rounds to 0; at p = 1 everything is +0), so the one
+ * selection is both masks and no hash is drawn.  g_eff16 = x, g_eff32 = x
+ * widened, db = its column sums in grl_relu_grad's row blocks and order; the
+ * operands, NULL-able outputs, workspace and empty cases are
+ * grl_relu_grad_bf16's.  One rounding, the bf16-output epilogue's.           */
+int grl_relu_grad_bf16_scaled(const uint16_t* g, int64_t ldg,
+                              const uint16_t* relu_out, int64_t ldo,
+                              uint16_t* g_eff16, int64_t lde, float* g_eff32,
+                              float* db, int64_t M, int32_t C, float scale,
+                              void* workspace, size_t workspace_bytes,
+                              grl_stream_t stream);
 
 /* emb1: Linear(K -> C) (+ReLU) over sparse bag-of-characters rows
  * (drop_robust_gcn.py:36,64; rows from TextlineEncoding,
