@@ -574,6 +574,29 @@ __global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_bf16o_kernel(
 #undef GRL_WS_BF16
 }
 
+// graphconv_ws_bf16o_kernel whose Zout holds bf16 bits too
+// (grl_graphconv_fwd_train_bf16_z16): the gather waves round the copy of a
+// finished row that goes to HBM (8 B a lane, ldz counted in bf16 elements);
+// the ring, and so out, is that kernel's.  The forward form only.
+template <int KS, bool VALS, int FV = 1, int PROD = 8>
+__global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_bf16oz_kernel(
+    int64_t M, int L, int hs, const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
+    const float* __restrict__ vals, uint64_t edge_base, uint64_t self_base, const uint16_t* __restrict__ X,
+    int64_t ldx, const uint16_t* __restrict__ Wf, const float* __restrict__ bias, int relu,
+    uint16_t* __restrict__ out, int C, DropDev de, int64_t num_tiles, uint16_t* __restrict__ Zout, int64_t ldz,
+    int spin_limit, int* __restrict__ status, int64_t self_row0, int64_t ldo) {
+  constexpr bool EID = false;
+  const int32_t* const eid = nullptr;
+  const int64_t self_rows = M;
+#define GRL_WS_BF16 1
+#define GRL_WS_OUT16 1
+#define GRL_WS_Z16 1
+#include "graphconv_ws_body.inc"
+#undef GRL_WS_Z16
+#undef GRL_WS_OUT16
+#undef GRL_WS_BF16
+}
+
 // The data-gradient form over a bf16 gradient table, writing bf16 rows
 // (grl_graphconv_bwd_data_bf16): graphconv_ws_kernel's EID form -- entry e's
 // DropEdge id through eid, the self term for rows < self_rows -- with
@@ -644,8 +667,8 @@ __device__ int g_grl_sticky;  // WS_WHO_* bits of the calls whose outputs were p
 
 constexpr int WS_WHO_FWD = 1, WS_WHO_FWD_TRAIN = 2, WS_WHO_BWD_DATA = 4, WS_WHO_FWD_BF16 = 8,
               WS_WHO_FWD_TRAIN_BF16 = 16, WS_WHO_FWD_BF16_TO_BF16 = 32, WS_WHO_FWD_TRAIN_BF16_TO_BF16 = 64,
-              WS_WHO_BWD_DATA_BF16 = 128;
-constexpr int WS_WHO_COUNT = 8;
+              WS_WHO_BWD_DATA_BF16 = 128, WS_WHO_FWD_TRAIN_BF16_Z16 = 256;
+constexpr int WS_WHO_COUNT = 9;
 
 __global__ void ws_poison_kernel(const int* __restrict__ status, float* __restrict__ a, int64_t na,
                                  float* __restrict__ b, int64_t nb, int who) {
@@ -680,18 +703,27 @@ static const char* who_name(int who) {
          : who == WS_WHO_FWD_TRAIN_BF16    ? "grl_graphconv_fwd_train_bf16"
          : who == WS_WHO_FWD_BF16_TO_BF16  ? "grl_graphconv_fwd_bf16_to_bf16"
          : who == WS_WHO_BWD_DATA_BF16     ? "grl_graphconv_bwd_data_bf16"
+         : who == WS_WHO_FWD_TRAIN_BF16_Z16 ? "grl_graphconv_fwd_train_bf16_z16"
                                            : "grl_graphconv_fwd_train_bf16_to_bf16";
 }
 
-// a: the call's out, float [M, C] contiguous or uint16_t (bf16 bits) [M, C] with row stride ldo
-template <typename OT>
-static int graphconv_status(const int* status, OT* a, int64_t M, int C, int64_t ldo, float* b, int64_t nb,
+// a: the call's out, float [M, C] contiguous or uint16_t (bf16 bits) [M, C] with row stride ldo; b: its Z / G_agg
+// of nb elements, float or (grl_graphconv_fwd_train_bf16_z16) bf16 bits, poisoned as one more bf16 array of a row
+template <typename OT, typename ZT = float>
+static int graphconv_status(const int* status, OT* a, int64_t M, int C, int64_t ldo, ZT* b, int64_t nb,
                             hipStream_t st, int who) {
   const bool sync = opt(OPT_WS_STATUS_SYNC) != 0;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   if (sync) GRL_HIP(hipStreamIsCapturing(st, &cs));
   if (!sync || cs != hipStreamCaptureStatusNone) {
-    if constexpr (std::is_same<OT, uint16_t>::value)
+    if constexpr (std::is_same<ZT, uint16_t>::value) {
+      static_assert(std::is_same<OT, uint16_t>::value, "a bf16 Z: with a bf16 out only");
+      hipLaunchKernelGGL(ws_poison_bf16_kernel, dim3(1024), dim3(256), 0, st, status, a, M, C, ldo,
+                         static_cast<float*>(nullptr), (int64_t)0, who);
+      if (b && M > 0)  // Z [M, nb / M] contiguous
+        hipLaunchKernelGGL(ws_poison_bf16_kernel, dim3(1024), dim3(256), 0, st, status, b, M, (int)(nb / M), nb / M,
+                           static_cast<float*>(nullptr), (int64_t)0, who);
+    } else if constexpr (std::is_same<OT, uint16_t>::value)
       hipLaunchKernelGGL(ws_poison_bf16_kernel, dim3(1024), dim3(256), 0, st, status, a, M, C, ldo, b, b ? nb : 0, who);
     else
       hipLaunchKernelGGL(ws_poison_kernel, dim3(1024), dim3(256), 0, st, status, a, M * C, b, b ? nb : 0, who);
@@ -714,22 +746,29 @@ static int graphconv_status(const int* status, OT* a, int64_t M, int C, int64_t 
 // grid = one workgroup per CU (at most the tiles).  The bf16 forward kernels
 // have no eid / self_rows arguments.  OT = uint16_t (a bf16 table only): out
 // holds bf16 bits with row stride ldo (graphconv_ws_bf16o_kernel, _bf16g_);
-// OT = float: out is [M, C] contiguous and ldo is not looked at.
-template <typename XT, bool EID, typename OT = float>
+// OT = float: out is [M, C] contiguous and ldo is not looked at.  ZT =
+// uint16_t (a bf16 out, the forward only): Z holds bf16 bits, ldz counts them
+// (graphconv_ws_bf16oz_kernel).
+template <typename XT, bool EID, typename OT = float, typename ZT = float>
 static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M, int L, int hs,
                       const GrlTypedCsr* g, const XT* X, int64_t ldx, const uint16_t* Wf, const float* bias,
-                      int relu, OT* out, int64_t ldo, DropDev d, int64_t tiles, float* Z, int64_t ldz,
+                      int relu, OT* out, int64_t ldo, DropDev d, int64_t tiles, ZT* Z, int64_t ldz,
                       const int32_t* eid, int64_t self_rows, int spin, int* status) {
   constexpr bool BF16 = std::is_same<XT, uint16_t>::value;
   constexpr bool OUT16 = std::is_same<OT, uint16_t>::value;
+  constexpr bool Z16 = std::is_same<ZT, uint16_t>::value;
   static_assert(!(BF16 && EID) || OUT16, "the data-gradient form over a bf16 table writes a bf16 dX only");
   static_assert(!OUT16 || BF16, "bf16 output: over a bf16 table only");
+  static_assert(!Z16 || (OUT16 && !EID), "bf16 Z: the forward with a bf16 out only");
 #define GRL_WS_HEAD                                                                                                \
   grid, dim3(64 * WS_WAVES), 0, st, M, L, hs, g->rowptr, g->colidx, g->vals, g->edge_id_base, g->self_id_base, X, \
       ldx, Wf, bias, relu, out, C, d, tiles, Z, ldz
 #define GRL_WS_INST(KS_, VALS_, FV_, PROD_)                                                                       \
   do {                                                                                                            \
-    if constexpr (OUT16 && EID)                                                                                   \
+    if constexpr (Z16)                                                                                            \
+      hipLaunchKernelGGL((graphconv_ws_bf16oz_kernel<KS_, VALS_, FV_, PROD_>), GRL_WS_HEAD, spin, status,         \
+                         g->self_row0, ldo);                                                                      \
+    else if constexpr (OUT16 && EID)                                                                              \
       hipLaunchKernelGGL((graphconv_ws_bf16g_kernel<KS_, VALS_, FV_, PROD_>), GRL_WS_HEAD, eid, self_rows, spin,  \
                          status, g->self_row0, ldo);                                                              \
     else if constexpr (OUT16)                                                                                     \
@@ -775,13 +814,15 @@ static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M
 
 // XT = float: X is the fp32 table; XT = uint16_t: bf16 bits, always on the
 // persistent kernel (there is no bf16 phase-alternating kernel).  OT =
-// uint16_t (a bf16 table only): out holds bf16 bits, ldo apart a row.
-template <typename XT, typename OT>
+// uint16_t (a bf16 table only): out holds bf16 bits, ldo apart a row.  ZT =
+// uint16_t (a bf16 out only): Z holds bf16 bits (grl_graphconv_fwd_train_bf16_z16).
+template <typename XT, typename OT, typename ZT = float>
 static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, const float* W,
                                const float* bias, int C, int relu, OT* out, int64_t ldo, const GrlDropEdge* de,
-                               void* ws, hipStream_t st, float* Z = nullptr) {
+                               void* ws, hipStream_t st, ZT* Z = nullptr) {
   constexpr bool BF16 = std::is_same<XT, uint16_t>::value;
   constexpr bool OUT16 = std::is_same<OT, uint16_t>::value;
+  constexpr bool Z16 = std::is_same<ZT, uint16_t>::value;
   static_assert(!OUT16 || BF16, "bf16 output: a bf16 table only");
   const int hs = g->has_self ? 1 : 0;
   const int64_t K = (int64_t)segments(g) * F;
@@ -804,11 +845,12 @@ static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, i
     int* status = ws_status(ws, K, C);
     const int spin = ws_spin_limit();
     GRL_HIP(hipMemsetAsync(status, 0, sizeof(int), st));
-    launch_ws<XT, false, OT>(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu, out,
-                             ldo, d, ws_tiles, Z, ldz, nullptr, M, spin, status);
+    launch_ws<XT, false, OT, ZT>(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu,
+                                 out, ldo, d, ws_tiles, Z, ldz, nullptr, M, spin, status);
     GRL_LAUNCH_CHECK();
     return graphconv_status(status, out, M, C, ldo, Z, M * ldz, st,
-                            OUT16  ? (Z ? WS_WHO_FWD_TRAIN_BF16_TO_BF16 : WS_WHO_FWD_BF16_TO_BF16)
+                            Z16    ? WS_WHO_FWD_TRAIN_BF16_Z16
+                            : OUT16 ? (Z ? WS_WHO_FWD_TRAIN_BF16_TO_BF16 : WS_WHO_FWD_BF16_TO_BF16)
                             : BF16 ? (Z ? WS_WHO_FWD_TRAIN_BF16 : WS_WHO_FWD_BF16)
                                    : (Z ? WS_WHO_FWD_TRAIN : WS_WHO_FWD));
   }
@@ -1182,6 +1224,64 @@ extern "C" int grl_graphconv_fwd_train_bf16_to_bf16(const GrlTypedCsr* g, const 
                                                     void* workspace, size_t workspace_bytes, grl_stream_t stream) {
   return graphconv_fwd_train("grl_graphconv_fwd_train_bf16_to_bf16", g, X, ldx, F, W, bias, C, relu, out, ldo, Z, de,
                              workspace, workspace_bytes, stream);
+}
+
+// ---- grl_graphconv_fwd_train_bf16_z16: the bf16-output training forward
+// whose Z holds bf16 bits too.  One kernel where the bf16-output rule holds and
+// a Z row takes the gather waves' 8 B stores (K % 4 == 0 there); elsewhere the
+// bf16 SpMM into an fp32 Z at the head of the workspace, the linear into an
+// fp32 [M, C] behind it, and the rounding pass over each.
+static bool z16_one_kernel(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, const float* W, int C,
+                           const uint16_t* out, int64_t ldo, const uint16_t* Z) {
+  return fused_path_out16(g, X, ldx, F, W, C, out, ldo) && reinterpret_cast<uintptr_t>(Z) % 8 == 0;
+}
+
+static size_t z16_two_kernel_ws(const GrlTypedCsr* g, int64_t K, int C) {
+  return ws_align((size_t)g->num_rows * (size_t)K * 4) + out16_scratch_bytes(g, C) +
+         grl_linear_fwd_ex_workspace_size(g->num_rows, (int32_t)K, C, g->path_rows);
+}
+
+extern "C" size_t grl_graphconv_fwd_train_bf16_z16_workspace_query(const GrlTypedCsr* g, const uint16_t* X,
+                                                                  int64_t ldx, int32_t F, const float* W, int32_t C,
+                                                                  const uint16_t* out, int64_t ldo,
+                                                                  const uint16_t* Z) {
+  if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0 || ldo < C) return 0;
+  const int64_t K = (int64_t)segments(g) * F;
+  if (K > 2147483647LL) return 0;
+  if (z16_one_kernel(g, X, ldx, F, W, C, out, ldo, Z)) return graphconv_fused_ws_bytes(K, C);
+  return z16_two_kernel_ws(g, K, C);
+}
+
+extern "C" int grl_graphconv_fwd_train_bf16_z16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+                                                const float* W, const float* bias, int32_t C, int32_t relu,
+                                                uint16_t* out, int64_t ldo, uint16_t* Z, const GrlDropEdge* de,
+                                                void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  const char* const who = "grl_graphconv_fwd_train_bf16_z16";
+  TraceRange trace_(who);
+  int32_t K = 0;
+  int rc = graphconv_fwd_check(who, g, X, ldx, F, W, C, out && Z, workspace, &K);
+  if (rc) return rc;
+  rc = out16_check(who, X, out, ldo, C);
+  if (rc) return rc;
+  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(Z) % 2 == 0, "%s: Z holds 2-byte elements and must be 2-B aligned", who);
+  if (g->num_rows == 0) return rc;
+  const int64_t M = g->num_rows;
+  hipStream_t st = as_stream(stream);
+  if (z16_one_kernel(g, X, ldx, F, W, C, out, ldo, Z) && workspace &&
+      workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, ldo, de, workspace, st, Z);
+  const size_t zfull = ws_align((size_t)M * (size_t)K * 4), scratch = out16_scratch_bytes(g, C);
+  const size_t need = z16_two_kernel_ws(g, K, C);
+  if (!workspace || workspace_bytes < need) GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
+  char* ws = static_cast<char*>(workspace);
+  float* Z32 = reinterpret_cast<float*>(ws);
+  float* lin_out = reinterpret_cast<float*>(ws + zfull);
+  rc = spmm_fwd(g, X, ldx, F, Z32, de, stream);
+  if (!rc)
+    rc = grl_linear_fwd_ex(Z32, K, W, 0, bias, lin_out, M, K, C, relu, g->path_rows, ws + zfull + scratch,
+                           workspace_bytes - zfull - scratch, stream);
+  if (!rc) rc = round_rows_bf16(lin_out, M, C, out, ldo, st);
+  return rc ? rc : round_rows_bf16(Z32, M, K, Z, (int64_t)K, st);
 }
 
 extern "C" int32_t grl_graphconv_bwd_data_shape_ok(int64_t rows, int32_t num_types, int32_t has_self, int32_t C,

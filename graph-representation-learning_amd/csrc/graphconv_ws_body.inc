@@ -5,7 +5,9 @@
 // GRL_WS_BF16 1) = graphconv_ws_bf16o_kernel, whose epilogue alone differs
 // (out holds bf16 bits, ldo apart a row), or -- with EID true and eid /
 // self_rows real arguments -- graphconv_ws_bf16g_kernel, the data-gradient
-// form of that kernel.  Textual sharing, not a function
+// form of that kernel.  GRL_WS_Z16: 1 (with both others 1, the forward form)
+// = graphconv_ws_bf16oz_kernel, whose gather waves' copy of a finished row to
+// Zout alone differs (bf16 bits; not defined = 0).  Textual sharing, not a function
 // template: the fp32 kernels' machine code is pinned
 // (tests/test_codegen_pin.py); an inlined function template around the body,
 // and a traits class around the loads alone, each moved every one of them,
@@ -155,6 +157,21 @@
 #endif
           // training forward (Zout): the row also goes to HBM for the weight
           // gradient, with non-temporal stores as spmm_kernel's
+#if GRL_WS_Z16
+          // GRL_WS_Z16: Zout holds bf16 bits (ldz counts them).  The ring keeps the unrounded fp32 row, so out
+          // does not move; the HBM copy alone is rounded to nearest even, 8 B a lane instead of 16.
+          uint16_t* const zrow = Zout ? Zout + rw0 * ldz + (int64_t)s * F + hv * FVW + col : nullptr;
+          auto flush = [&](int r, const float4& v) {  // r: the wave's row
+            if (col_ok) {
+              *reinterpret_cast<float4*>(dst + r * WS_LDF) = v;
+              if (zrow && r < nvalid) {
+                typedef uint32_t z_u32x2_t __attribute__((ext_vector_type(2)));
+                z_u32x2_t t = {cvt_pk_bf16(v.x, v.y), cvt_pk_bf16(v.z, v.w)};
+                __builtin_nontemporal_store(t, reinterpret_cast<z_u32x2_t*>(zrow + (int64_t)r * ldz));
+              }
+            }
+          };
+#else
           float* const zrow = Zout ? Zout + rw0 * ldz + (int64_t)s * F + hv * FVW + col : nullptr;
           auto flush = [&](int r, const float4& v) {  // r: the wave's row
             if (col_ok) {
@@ -165,6 +182,7 @@
               }
             }
           };
+#endif
           if (s < hs) {
             // identity block of A_pre (robust_gcn.py:58-65): the rows' own features, SC rows at a time
             // (a rolled loop: unrolled, the rows' loads and uniform DropEdge hashes crowd the registers)

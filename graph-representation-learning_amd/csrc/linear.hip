@@ -1221,6 +1221,164 @@ __global__ __launch_bounds__(512) void gemm_x3t_kernel(GemmArgs p, const uint16_
   }
 }
 
+// ---------------------------------------------------------------------------
+// x1t: gemm_x3t_kernel for a Z stored as bf16 too (grl_linear_bwd_weight_bf16zg,
+// DESIGN.md §4.21).  z16(k, m) = bf16 bits at z16[k * p.lda + m], g16(k, n) at
+// g16[k * p.ldb + n] (p.A, p.B unused).  Both operands are one plane: their
+// rows go into LDS as loaded (8 B a lane per staged row, no VALU at all), a
+// stage is one A plane + one B plane (16 KB), a K16 step costs a wave 4 + 2
+// fragment reads and 8 MFMAs (x1_mfma).  What fixes the order in which a dW
+// element is summed is gemm_x6t_kernel's: the 32x32x16 instruction, the tile,
+// the K16 steps in ascending order, the stages' swizzle and transposed reads,
+// the zeroing of rows past the split's end, the epilogue and the host's split
+// rule; so the bits are that kernel's on the widened operands.  A step is 8
+// MFMAs a wave, far less than an HBM miss: the loads run GRL_X1T_NR K16 steps
+// ahead of their LDS stash in register sets of 8 VGPRs each (1, 2 and 4 were
+// measured, §4.21).  Preconditions (x1t_ok): z16 and g16 8 B-aligned, lda % 4
+// == 0, ldb % 4 == 0, M, N multiples of 4.
+#if !defined(GRL_DIAG) || !defined(GRL_X1T_NR)
+#undef GRL_X1T_NR
+#define GRL_X1T_NR 4
+#endif
+constexpr int X1_STAGE = 2 * X6_PLANE;  // A's plane, then B's
+
+template <int EPI>
+__global__ __launch_bounds__(512) void gemm_x1t_kernel(GemmArgs p, const uint16_t* __restrict__ z16,
+                                                       const uint16_t* __restrict__ g16) {
+  __shared__ __attribute__((aligned(16))) uint16_t smem[2 * X1_STAGE];  // 2 stages x (A, B) planes x 8 KB
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;
+  const int l32 = lane & 31, h = lane >> 5;
+  int64_t mi, ni, zi;
+  tile_of(p, mi, ni, zi);
+  const int64_t m0 = mi * LB_M, n0 = ni * LB_N;
+  const int64_t kbeg = zi * p.k_per_split;
+  const int64_t kend = min(p.K, kbeg + p.k_per_split);
+  const int64_t nk = kend > kbeg ? (kend - kbeg + X6_K - 1) / X6_K : 0;
+
+  // staging: 4-column group f = tid + 512 i of each operand: k row f >> 6, columns (f & 63) * 4 (a uint2 = 4
+  // bf16); the staged k rows are wave-uniform, as in gemm_x6t_kernel
+  const int kr0 = __builtin_amdgcn_readfirstlane(tid >> 6), kr1 = kr0 + 8;
+  const int col = (tid & 63) * 4;
+  const int64_t am = min<int64_t>(m0 + col, p.M - 4), bn = min<int64_t>(n0 + col, p.N - 4);
+  const uint16_t* __restrict__ a_base = z16 + am;
+  const uint16_t* __restrict__ b_base = g16 + bn;
+  const int st_off0 = kr0 * 256 + (col ^ ((kr0 & 3) << 5));
+  const int st_off1 = kr1 * 256 + (col ^ ((kr1 & 3) << 5));
+  // register sets of staged rows: set j holds step t's rows for t = j (mod NR)
+  constexpr int NR = GRL_X1T_NR;
+  static_assert(NR == 1 || NR == 2 || NR == 4, "the K16 loop is unrolled by four");
+  uint2 ra0[NR], ra1[NR], rb0[NR], rb1[NR];
+  bool in0[NR], in1[NR];  // the staged rows lie inside this split's K range
+  const uint2 zero2 = make_uint2(0u, 0u);
+  // rows past the split's end: loaded clamped (from kbeg), zeroed when stashed (gemm_x6t_kernel's reason)
+#define X1T_LOAD(t, j)                                                                                    \
+  do {                                                                                                    \
+    const int64_t k_ = kbeg + (t) * X6_K;                                                                 \
+    in0[j] = k_ + kr0 < kend;                                                                             \
+    in1[j] = k_ + kr1 < kend;                                                                             \
+    const int64_t r0_ = in0[j] ? k_ + kr0 : kbeg;                                                         \
+    const int64_t r1_ = in1[j] ? k_ + kr1 : kbeg;                                                         \
+    ra0[j] = *reinterpret_cast<const uint2*>(a_base + r0_ * p.lda);                                       \
+    ra1[j] = *reinterpret_cast<const uint2*>(a_base + r1_ * p.lda);                                       \
+    rb0[j] = *reinterpret_cast<const uint2*>(b_base + r0_ * p.ldb);                                       \
+    rb1[j] = *reinterpret_cast<const uint2*>(b_base + r1_ * p.ldb);                                       \
+  } while (0)
+#define X1T_STASH(st, j)                                                                                  \
+  do {                                                                                                    \
+    if (!in0[j]) ra0[j] = rb0[j] = zero2; /* wave-uniform: only a split's last K16 step branches */       \
+    if (!in1[j]) ra1[j] = rb1[j] = zero2;                                                                 \
+    *reinterpret_cast<uint2*>((st) + st_off0) = ra0[j];                                                   \
+    *reinterpret_cast<uint2*>((st) + st_off1) = ra1[j];                                                   \
+    *reinterpret_cast<uint2*>((st) + X6_PLANE + st_off0) = rb0[j];                                        \
+    *reinterpret_cast<uint2*>((st) + X6_PLANE + st_off1) = rb1[j];                                        \
+  } while (0)
+
+  // this lane's transposed-read coordinates: k = 8h + ((lane & 15) >> 2),
+  // column = block base + 16 ((lane >> 4) & 1) + 4 (lane & 3)
+  const int tk = 8 * h + ((lane & 15) >> 2);
+  const int tc = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+
+  if (nk > 0) {
+    X1T_LOAD(0, 0);
+    X1T_STASH(smem, 0);
+#pragma unroll
+    for (int j = 1; j <= NR; ++j)
+      if (nk > j) X1T_LOAD(j, j % NR);
+  }
+  __syncthreads();
+  {
+    const lds_u16* s3 = (const lds_u16*)smem;
+    const int sx = (tk & 3) << 5;
+    int oa[4], ob[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) oa[i] = tk * 256 + ((wm * 128 + i * 32 + tc) ^ sx);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) ob[j] = tk * 256 + ((wn * 64 + j * 32 + tc) ^ sx);
+    // step t reads LDS stage S = t & 1 and stashes register set J = (t + 1) % NR into the other stage: both
+    // constants of the body (the loop is unrolled by four)
+    auto step = [&](int64_t t, auto stage, auto rset) {
+      constexpr int S = decltype(stage)::value;
+      constexpr int J = decltype(rset)::value;
+      const lds_u16* cur = s3 + S * X1_STAGE;
+      auto frag = [](const lds_u16* p0) { return tr8s(p0, p0 + 4 * 256); };  // (second block row: 4 k rows on)
+      bf16x8_t a_[4], b_[2];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a_[i] = frag(cur + oa[i]);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) b_[j] = frag(cur + X6_PLANE + ob[j]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) x1_mfma(acc[i][j], a_[i], b_[j]);
+      if (t + 1 < nk) {
+        X1T_STASH(smem + (S ^ 1) * X1_STAGE, J);  // the other stage: last read in step t-1
+        if (t + 1 + NR < nk) X1T_LOAD(t + 1 + NR, J);
+      }
+      __syncthreads();
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    using J0 = std::integral_constant<int, 1 % NR>;
+    using J1 = std::integral_constant<int, 2 % NR>;
+    using J2 = std::integral_constant<int, 3 % NR>;
+    using J3 = std::integral_constant<int, 4 % NR>;
+    int64_t t = 0;
+    for (; t + 3 < nk; t += 4) {
+      step(t, I0{}, J0{});
+      step(t + 1, I1{}, J1{});
+      step(t + 2, I0{}, J2{});
+      step(t + 3, I1{}, J3{});
+    }
+    if (t < nk) step(t, I0{}, J0{});
+    if (t + 1 < nk) step(t + 1, I1{}, J1{});
+    if (t + 2 < nk) step(t + 2, I0{}, J2{});
+  }
+#undef X1T_LOAD
+#undef X1T_STASH
+  float* Cz = p.C + (EPI == EPI_SLAB ? zi * p.M * p.ldc : 0);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int64_t gn = n0 + wn * 64 + j * 32 + l32;
+    if (gn >= p.N) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t gm = m0 + wm * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (gm < p.M) Cz[gm * p.ldc + gn] = acc[i][j][r];
+      }
+  }
+}
+
 constexpr int GEMM_BK = 32;
 
 template <bool A_KC, bool B_KC, int EPI, int TBN = BN>
@@ -1809,6 +1967,90 @@ extern "C" int grl_linear_bwd_weight_bf16g(const float* Z, int64_t ldz, const ui
     hipLaunchKernelGGL(gemm_x3t_kernel<EPI_SLAB>, grid, dim3(512), 0, st, a, g);
   else
     hipLaunchKernelGGL(gemm_x3t_kernel<EPI_STORE>, grid, dim3(512), 0, st, a, g);
+  GRL_LAUNCH_CHECK();
+  if (used > 1) {
+    const int64_t n = (int64_t)K * C;
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 65536)), dim3(256), 0,
+                       st, slab, n, used, dW);
+    GRL_LAUNCH_CHECK();
+  }
+  if (db) {
+    const int zs = colsum_splits(M);
+    float* part = slab + (size_t)wgt_slab_splits(M, K, C) * K * C;
+    const int64_t rows_per = ceil_div(std::max<int64_t>(M, 1), zs);
+    hipLaunchKernelGGL(colsum_partial_bf16_kernel, dim3((unsigned)ceil_div(C, 256), (unsigned)zs), dim3(256), 0, st, g,
+                       ldg, M, (int64_t)C, rows_per, part);
+    GRL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs,
+                       db);
+    GRL_LAUNCH_CHECK();
+  }
+  return GRL_OK;
+}
+
+namespace grl {
+namespace {
+// x1t (dW from a Z and a g both stored as bf16) selection: gemm_x6t_kernel's
+// shape rule, each operand's rows on the 8 B loads of four bf16, and the
+// dw_bf16z path option
+bool x1t_ok(const uint16_t* Z, int64_t ldz, const uint16_t* g, int64_t ldg, int64_t M, int64_t K, int64_t C) {
+  return opt(OPT_DW_BF16Z) != 0 && x6t_shape_ok(M, K, C) && reinterpret_cast<uintptr_t>(Z) % 8 == 0 &&
+         ldz % 4 == 0 && reinterpret_cast<uintptr_t>(g) % 8 == 0 && ldg % 4 == 0;
+}
+}  // namespace
+}  // namespace grl
+
+extern "C" size_t grl_linear_bwd_weight_bf16zg_workspace_query(const uint16_t* Z, int64_t ldz, const uint16_t* g,
+                                                               int64_t ldg, int64_t M, int32_t K, int32_t C) {
+  if (!Z || !g || M <= 0 || K <= 0 || C <= 0 || ldz < K || ldg < C) return 0;
+  return grl::x1t_ok(Z, ldz, g, ldg, M, K, C) ? grl_linear_bwd_weight_workspace_size(M, K, C) : 0;
+}
+
+extern "C" int grl_linear_bwd_weight_bf16zg(const uint16_t* Z, int64_t ldz, const uint16_t* g, int64_t ldg, float* dW,
+                                            float* db, int64_t M, int32_t K, int32_t C, void* workspace,
+                                            size_t workspace_bytes, grl_stream_t stream) {
+  TraceRange trace_("grl_linear_bwd_weight_bf16zg");
+  GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0, "grl_linear_bwd_weight_bf16zg: negative size");
+  GRL_CHECK_ARG(ldz >= K && ldg >= C,
+                "grl_linear_bwd_weight_bf16zg: need ldz >= K and ldg >= C (ldz=%lld K=%d ldg=%lld C=%d)",
+                (long long)ldz, K, (long long)ldg, C);
+  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(Z) % 2 == 0 && reinterpret_cast<uintptr_t>(g) % 2 == 0,
+                "grl_linear_bwd_weight_bf16zg: Z and g must be 2-B aligned");
+  if (K == 0 || C == 0) return GRL_OK;
+  if (M == 0) {  // no rows (an empty node-range shard): dW = 0, db = 0
+    GRL_CHECK_ARG(dW, "grl_linear_bwd_weight_bf16zg: NULL pointer");
+    hipStream_t st = as_stream(stream);
+    if (hipMemsetAsync(dW, 0, (size_t)K * C * sizeof(float), st) != hipSuccess ||
+        (db && hipMemsetAsync(db, 0, (size_t)C * sizeof(float), st) != hipSuccess))
+      GRL_FAIL(GRL_E_HIP, "grl_linear_bwd_weight_bf16zg: hipMemsetAsync failed");
+    return GRL_OK;
+  }
+  GRL_CHECK_ARG(Z && g && dW, "grl_linear_bwd_weight_bf16zg: NULL pointer");
+  if (!x1t_ok(Z, ldz, g, ldg, M, K, C))
+    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_linear_bwd_weight_bf16zg: outside the bf16-Z dW path (M %lld, K %d, C %d, "
+             "the operands' alignment or the dw_bf16z / gemm_x6 options; see "
+             "grl_linear_bwd_weight_bf16zg_workspace_query)", (long long)M, K, C);
+  const size_t need = grl_linear_bwd_weight_workspace_size(M, K, C);
+  if (!workspace || workspace_bytes < need)
+    GRL_FAIL(GRL_E_WORKSPACE, "grl_linear_bwd_weight_bf16zg: workspace %zu < %zu", workspace_bytes, need);
+  hipStream_t st = as_stream(stream);
+  float* slab = static_cast<float*>(workspace);
+  // gemm_x6t_kernel's launch (grl_linear_bwd_weight): the same splits, tile order and slab reduce
+  GemmArgs a = gemm_args(nullptr, ldz, nullptr, ldg, nullptr, C, K, C, M);
+  const int splits = x6t_splits(M, K, C);
+  a.C = splits > 1 ? slab : dW;
+  a.k_per_split = ceil_div(ceil_div(M, splits), X6_K) * X6_K;
+  const int used = (int)ceil_div(M, a.k_per_split);
+  a.mt = ceil_div(a.M, LB_M);
+  a.nt = ceil_div(a.N, LB_N);
+  a.zt = used;
+  a.inner_n = 0;
+  GRL_CHECK_ARG(a.mt * a.nt * a.zt < 2147483647LL, "gemm: grid too large");
+  const dim3 grid((unsigned)(a.mt * a.nt * a.zt));
+  if (used > 1)
+    hipLaunchKernelGGL(gemm_x1t_kernel<EPI_SLAB>, grid, dim3(512), 0, st, a, Z, g);
+  else
+    hipLaunchKernelGGL(gemm_x1t_kernel<EPI_STORE>, grid, dim3(512), 0, st, a, Z, g);
   GRL_LAUNCH_CHECK();
   if (used > 1) {
     const int64_t n = (int64_t)K * C;

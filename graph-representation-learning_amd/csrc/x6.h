@@ -110,6 +110,16 @@ __device__ __forceinline__ void x3_mfma(f32x16& acc, const bf16x8_t (&a)[3], bf1
   mfma_bf16(acc, a[0], b);
 }
 
+// acc += a b for an a and a b that are each ONE bf16 plane (both stored as
+// bf16): the single product a0 b.  It is bitwise x3_mfma on an a whose planes
+// 1 and 2 are +0 (what split3 gives for a value that is a bf16 already: both
+// residuals are v - v = +0): that sequence runs a2 b and a1 b first, and each
+// adds sums of +-0 products to an accumulator that starts at +0 and, under
+// round to nearest, is never -0 afterwards (x + (+-0) = x for x != 0, and
+// +0 + (-0) = +0), so the accumulator a0 b meets is the one it meets here
+// (DESIGN.md §4.19's argument, applied to the other operand: §4.21).
+__device__ __forceinline__ void x1_mfma(f32x16& acc, bf16x8_t a, bf16x8_t b) { mfma_bf16(acc, a, b); }
+
 // ---- LDS-DMA ----------------------------------------------------------------
 // global -> LDS DMA of one 16 B chunk per lane (lane l lands at lds_base + 16 l).
 // Issued from asm so that hipcc's waitcnt pass neither sees nor waits on it

@@ -211,7 +211,18 @@ class GraphCNNDropEdge(BaseNetwork):
     their gradients.  The feature masks are those of the fp32 model (the same
     element ids and hash).  Everywhere else -- eval mode, a node-range shard, a
     dense A, the CPU, the default None -- this attribute is ignored and today's
-    path runs bit for bit."""
+    path runs bit for bit.
+
+    `train_z_dtype` (likewise an attribute; default None): with torch.bfloat16
+    AND the train_activation_dtype path above running, the three layers keep
+    their Z = A_drop X for the backward as bfloat16
+    (grl.ops.graph_conv(..., z_dtype=)): half the bytes held between the
+    passes, and dW one plane product on the two bf16 tables.  Logits, and every
+    gradient but the three h_weights', are bitwise those of train_z_dtype =
+    None; the h_weights gradients see Z rounded once to bfloat16.  Everywhere
+    else it is ignored and today's path runs bit for bit: fp32 training, eval,
+    shards, a dense A, the CPU, None, and pages of at most ROW_LINEAR_MIN_ROWS
+    rows (whose dropout is torch's, outside the fused bf16 node)."""
 
     def __init__(self, input_dim: int, output_dim: int, num_edges: int, net_size: int = 256,
                  use_attention: bool = True, dropedge_seed: Optional[int] = None):
@@ -226,6 +237,8 @@ class GraphCNNDropEdge(BaseNetwork):
         self.activation_dtype: Optional[torch.dtype] = None
         # torch.bfloat16: the GraphConv activations and the gradients between them bf16 in training (class docstring)
         self.train_activation_dtype: Optional[torch.dtype] = None
+        # torch.bfloat16: with train_activation_dtype, the layers' saved Z is bf16 too (class docstring)
+        self.train_z_dtype: Optional[torch.dtype] = None
         self.dropout = FeatureDropout(p=0.5, seed=dropedge_seed)
         self.edge_dropout = EdgeDropout(p=0.3, seed=dropedge_seed)
         self.gcn1 = GraphConv(self.net_size, self.net_size, num_edges)
@@ -323,10 +336,14 @@ class GraphCNNDropEdge(BaseNetwork):
         lead = emb.shape[:-1]
         bf16 = torch.bfloat16
         x0 = self.dropout(emb.reshape(-1, C).to(bf16))  # the one cast, then the bf16 dropout (:64)
-        g1 = self.gcn1.propagate(x0, self.edge_dropout(graph, ds), relu=True, dropout=self.dropout, out_dtype=bf16)
-        g2 = self.gcn2.propagate(g1, self.edge_dropout(graph, ds), relu=True, dropout=self.dropout, out_dtype=bf16)
+        # train_z_dtype: the saved Z bf16 too, where the layers run as the fused bf16 node (the hash-mask dropout)
+        zd = bf16 if self.train_z_dtype == bf16 and self.dropout._hash else None
+        g1 = self.gcn1.propagate(x0, self.edge_dropout(graph, ds), relu=True, dropout=self.dropout, out_dtype=bf16,
+                                 z_dtype=zd)
+        g2 = self.gcn2.propagate(g1, self.edge_dropout(graph, ds), relu=True, dropout=self.dropout, out_dtype=bf16,
+                                 z_dtype=zd)
         g3 = self.gcn3.propagate(torch.cat([g1, g2], dim=-1), self.edge_dropout(graph, ds), relu=True,
-                                 dropout=self.dropout, out_dtype=bf16)
+                                 dropout=self.dropout, out_dtype=bf16, z_dtype=zd)
         return torch.cat([g1, g3], dim=-1).float().view(*lead, 2 * C)
 
     def _head(self, x: torch.Tensor, graph, sharded: bool, pr: int) -> torch.Tensor:

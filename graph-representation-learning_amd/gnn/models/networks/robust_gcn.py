@@ -109,7 +109,7 @@ class GraphConv(nn.Module):
 
     # ------------------------------------------------------------- forward
     def propagate(self, V: torch.Tensor, graph, relu: bool = False, dropout=None, out: torch.Tensor = None,
-                  out_dtype=None) -> torch.Tensor:
+                  out_dtype=None, z_dtype=None) -> torch.Tensor:
         """Aggregate + linear (+ fused ReLU) on a ready TypedGraph, or on this
         rank's node-range shard of a graph (grl.dist.ShardedGraph: V holds the
         shard's rows; the halo exchange runs inside, the output rows are the
@@ -122,7 +122,9 @@ class GraphConv(nn.Module):
         the layer writes and returns -- with a bfloat16 V a bfloat16 one of any
         row stride, e.g. a column slice of the next layer's table
         (grl.ops.graph_conv_infer).  out_dtype: grl.ops.graph_conv's (a
-        bfloat16 output in a new tensor from a bfloat16 V)."""
+        bfloat16 output in a new tensor from a bfloat16 V).  z_dtype:
+        grl.ops.graph_conv's (torch.bfloat16 with out_dtype=torch.bfloat16: the Z
+        kept for the backward holds bf16), passed through on a TypedGraph."""
         lead = V.shape[:-1]
         if out is not None:
             if isinstance(graph, ShardedGraph) or torch.is_grad_enabled():
@@ -147,10 +149,10 @@ class GraphConv(nn.Module):
             fd = dropout.record(V.device)
             if fd is not None:
                 out = graph_conv(V, graph, self.h_weights, self.bias, relu=relu, recompute=self.recompute_aggregation,
-                                 out_dtype=out_dtype, fdrop=fd, row0=getattr(dropout, "row0", 0))
+                                 out_dtype=out_dtype, fdrop=fd, row0=getattr(dropout, "row0", 0), z_dtype=z_dtype)
                 return out.view(*lead, self.C)
         out = graph_conv(V, graph, self.h_weights, self.bias, relu=relu, recompute=self.recompute_aggregation,
-                         out_dtype=out_dtype)
+                         out_dtype=out_dtype, z_dtype=z_dtype)
         out = out.view(*lead, self.C)
         return dropout(out) if dropout is not None else out
 

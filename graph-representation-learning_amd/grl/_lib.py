@@ -173,6 +173,11 @@ SIGNATURES = {
     "grl_graphconv_fwd_train_bf16_to_bf16": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i32,
                                                       _c_i32, _c_vp, _c_i64, _c_vp, _P(GrlDropEdge), _c_vp, _c_size,
                                                       _c_vp]),
+    "grl_graphconv_fwd_train_bf16_z16_workspace_query": (_c_size, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp,
+                                                                   _c_i32, _c_vp, _c_i64, _c_vp]),
+    "grl_graphconv_fwd_train_bf16_z16": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _c_vp, _c_i32,
+                                                  _c_i32, _c_vp, _c_i64, _c_vp, _P(GrlDropEdge), _c_vp, _c_size,
+                                                  _c_vp]),
     "grl_linear_fwd_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32]),
     "grl_linear_fwd": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_vp, _c_size,
                                 _c_vp]),
@@ -195,6 +200,9 @@ SIGNATURES = {
     "grl_linear_bwd_weight_bf16g_workspace_query": (_c_size, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32]),
     "grl_linear_bwd_weight_bf16g": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32,
                                              _c_vp, _c_size, _c_vp]),
+    "grl_linear_bwd_weight_bf16zg_workspace_query": (_c_size, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32]),
+    "grl_linear_bwd_weight_bf16zg": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32,
+                                              _c_vp, _c_size, _c_vp]),
     "grl_dense_to_csr_workspace_size": (_c_size, [_c_i64]),
     "grl_dense_to_csr_rowptr": (_c_i32, [_c_vp, _c_i64, _c_i64, _c_i32, _P(_c_i64), _c_vp, _c_vp, _c_size, _c_vp]),
     "grl_dense_to_csr_fill": (_c_i32, [_c_vp, _c_i64, _c_i64, _c_i32, _P(_c_i64), _c_vp, _c_vp, _c_vp, _c_vp]),

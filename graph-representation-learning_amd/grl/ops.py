@@ -395,6 +395,40 @@ def linear_bwd_weight_bf16(Z2: torch.Tensor, g16: torch.Tensor, want_db: bool):
     return dW, db
 
 
+def linear_bwd_weight_bf16z(Z16: torch.Tensor, g16: torch.Tensor, want_db: bool):
+    """(dW, db) = (Z16^T g16, column sums of g16) with BOTH operands bfloat16 and
+    read as stored (grl_linear_bwd_weight_bf16zg: one plane product of the
+    split-bf16 dW GEMM per block, no split and no widened copy), bitwise
+    linear_bwd_weight(Z16.float(), g16.float(), None, want_db) -- or None where
+    that entry's workspace query is 0 (below the x6 size floor, an operand off
+    the 8 B grid, the dw_bf16z or gemm_x6 path option 0, ...); the caller then
+    widens Z16.  Nothing is allocated before the query.  Z16 [M, K] and g16
+    [M, C]: 2-D bfloat16 with unit column stride and a row stride of at least
+    their width (column slices of wider tables are read in place); g16 already
+    through the ReLU's mask."""
+    _require_device(g16, "linear_bwd_weight_bf16z g")
+    for t, what in ((Z16, "Z"), (g16, "g")):
+        if (t.dtype != torch.bfloat16 or t.dim() != 2 or (t.shape[1] > 0 and t.stride(1) != 1) or not _rows_apart(t)
+                or t.device != g16.device):
+            raise _lib.GrlError(f"linear_bwd_weight_bf16z: {what} must be a 2-D bfloat16 tensor on {g16.device} with "
+                                "unit column stride and a row stride of at least its width (an expanded tensor: "
+                                ".contiguous() first)")
+    if Z16.shape[0] != g16.shape[0]:
+        raise _lib.GrlError(f"linear_bwd_weight_bf16z: Z has {Z16.shape[0]} rows, g {g16.shape[0]}")
+    M, K = Z16.shape
+    C = g16.shape[1]
+    ws_bytes = _lib.lib().grl_linear_bwd_weight_bf16zg_workspace_query(Z16.data_ptr(), _ld(Z16), g16.data_ptr(),
+                                                                       _ld(g16), M, K, C)
+    if ws_bytes == 0:
+        return None
+    dW = torch.empty(K, C, dtype=torch.float32, device=g16.device)
+    db = torch.empty(C, dtype=torch.float32, device=g16.device) if want_db else None
+    ws = _workspace(ws_bytes, g16.device)
+    call("grl_linear_bwd_weight_bf16zg", Z16.data_ptr(), _ld(Z16), g16.data_ptr(), _ld(g16), dW.data_ptr(), _ptr(db), M,
+         K, C, _ptr(ws), ws_bytes, current_stream_handle(g16.device))
+    return dW, db
+
+
 class _GraphLinear(torch.autograd.Function):
     """out = Z W + b [ReLU]; backward on the same MFMA GEMM kernel with the
     ReLU mask fused into the operand loads (no g*mask temporary)."""
@@ -682,7 +716,7 @@ class _GraphConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b, relu: bool, recompute: bool,
-                out_bf16: bool = False, fdrop=None, row0: int = 0):
+                out_bf16: bool = False, fdrop=None, row0: int = 0, z_bf16: bool = False):
         Wc = W.contiguous()
         bc = b.contiguous() if b is not None else None
         # out_bf16 (a bf16 X on a TypedGraph: graph_conv checks): the layer's epilogue writes bf16
@@ -694,9 +728,12 @@ class _GraphConv(torch.autograd.Function):
             Z = None
             out = graph_conv_infer(X, graph, Wc, bc, relu, out=out)
         else:  # one kernel that also writes Z where it applies (grl_graphconv_fwd_train)
-            out, Z = graph_conv_fwd_train(X, graph, Wc, bc, relu, out=out)
+            # z_bf16 (out_bf16 on a TypedGraph: graph_conv checks): the saved Z holds bf16 too, half the bytes
+            out, Z = graph_conv_fwd_train(X, graph, Wc, bc, relu, out=out,
+                                          z_dtype=torch.bfloat16 if z_bf16 else None)
         ctx.graph, ctx.relu, ctx.has_b, ctx.xshape, ctx.xdtype = graph, relu, b is not None, X.shape, X.dtype
         ctx.recompute = recompute
+        ctx.z16 = Z is not None and Z.dtype == torch.bfloat16  # (never with recompute: X is what is kept)
         # fdrop (relu and out_bf16: graph_conv checks): the feature dropout in place on the fresh bf16 output, which
         # is then the one tensor returned and saved -- > 0 exactly where kept and open, so the backward needs the
         # record's scale alone (grl_relu_grad_bf16_scaled), no hash and no pre-dropout copy
@@ -719,6 +756,8 @@ class _GraphConv(torch.autograd.Function):
             res = _GraphConv._backward_bf16(ctx, g, Z, W, out, want_w, want_b)
             if res is not None:
                 return res
+        if ctx.z16:  # a bf16 saved Z on the widened path: widened once, exactly; the fp32 layer's backward on it
+            Z = Z.float()
         if ctx.fscale is not None:
             # the fused dropout where the bf16 data gradient does not apply: the masked, scaled bf16 gradient
             # first (one pass over g and the dropped output), then the widened path on it -- whose own mask
@@ -743,7 +782,7 @@ class _GraphConv(torch.autograd.Function):
                 del G_agg
                 dW = dWt.view(F, S, C).transpose(0, 1).reshape(S * F, C)
                 db = (db_pre if db_pre is not None else g_eff.sum(0)) if want_b else None
-                return dX.view(ctx.xshape), None, dW, db, None, None, None, None, None
+                return dX.view(ctx.xshape), None, dW, db, None, None, None, None, None, None
         if ctx.recompute and (want_w or (want_b and db_pre is None)):
             Z = spmm_forward(Z, ctx.graph)
         dW = db = dX = None
@@ -759,7 +798,7 @@ class _GraphConv(torch.autograd.Function):
             dW, db = linear_bwd_weight(Z, g, mask, want_b and db_pre is None)
         if db_pre is not None:
             db = db_pre
-        return dX, None, dW if want_w else None, db, None, None, None, None, None
+        return dX, None, dW if want_w else None, db, None, None, None, None, None, None
 
     @staticmethod
     def _backward_bf16(ctx, g: torch.Tensor, Z, W: torch.Tensor, out, want_w: bool, want_b: bool):
@@ -792,16 +831,23 @@ class _GraphConv(torch.autograd.Function):
         # below PREMASK_ROWS with a ReLU: there the widened path's GEMM masks on its loads in the fp32-MFMA
         # kernel, other bits.  Asked before the mask pass (which then skips its fp32 output) for the tensors as
         # they will be: the masked gradient and a recomputed Z are new contiguous tensors.
+        # A bf16 saved Z (ctx.z16): the bf16zg query is asked where the bf16g query is, and where it answers, dW is
+        # ONE plane product on the two tables as stored (linear_bwd_weight_bf16z); where it does not, Z is widened
+        # once (exactly) and the code below runs on it as on an fp32 saved Z.
         gemm = want_w or (want_b and not premask)
-        dw16 = False
+        dw16 = dwz = False
         if gemm and (premask or not relu):
             K = graph.segments * F
             g_at, ldg = (_FRESH_ADDRESS, C) if premask else (g2.data_ptr(), _ld(g2))
-            z_at, ldz = (_FRESH_ADDRESS, K) if ctx.recompute else (Z.data_ptr(), _ld(Z))
-            dw16 = _lib.lib().grl_linear_bwd_weight_bf16g_workspace_query(z_at, ldz, g_at, ldg, M, K, C) != 0
+            if ctx.z16:
+                dwz = _lib.lib().grl_linear_bwd_weight_bf16zg_workspace_query(Z.data_ptr(), _ld(Z), g_at, ldg, M, K,
+                                                                              C) != 0
+            if not dwz:
+                z_at, ldz = (_FRESH_ADDRESS, K) if ctx.recompute or ctx.z16 else (Z.data_ptr(), _ld(Z))
+                dw16 = _lib.lib().grl_linear_bwd_weight_bf16g_workspace_query(z_at, ldz, g_at, ldg, M, K, C) != 0
         g32 = mask = db_pre = None
         if premask:
-            g16, g32, db_pre = _relu_grad_bf16(g2, out, want_b, want_w and not dw16, scale=ctx.fscale)
+            g16, g32, db_pre = _relu_grad_bf16(g2, out, want_b, want_w and not (dw16 or dwz), scale=ctx.fscale)
         elif ctx.fscale is not None:
             # the fused dropout below PREMASK_ROWS: the scaled pass still makes the gradient (masked by the dropped
             # output, scaled, rounded once) and its fp32 copy for the dW GEMM, which keeps masking on its loads
@@ -810,14 +856,22 @@ class _GraphConv(torch.autograd.Function):
         else:
             g16 = torch.where(out > 0, g2, torch.zeros((), dtype=g2.dtype, device=g.device)) if relu else g2
         dX = _bwd_data_run(plan, g16, graph, W, F).view(ctx.xshape)
-        if not dw16:
+        if not (dw16 or dwz):
             del g16
         dW = db = None
         if gemm:
             if ctx.recompute:
                 Z = spmm_forward(Z, graph)
             res = None
-            if dw16:
+            if dwz:
+                res = linear_bwd_weight_bf16z(Z, g16, want_b and db_pre is None)
+            if ctx.z16 and res is None:
+                Z = Z.float()
+            if dwz:
+                if res is None:  # (the tensors are not as asked for: both widened, the same values)
+                    g32 = g16.float().contiguous()
+                del g16
+            elif dw16:
                 res = linear_bwd_weight_bf16(Z, g16, want_b and db_pre is None)
                 if res is None:  # (the tensors are not as asked for: the masked gradient widened, the same values)
                     g32 = g16.float().contiguous()
@@ -828,11 +882,11 @@ class _GraphConv(torch.autograd.Function):
             dW, db = res if res is not None else linear_bwd_weight(Z, g32, mask, want_b and db_pre is None)
         if db_pre is not None:
             db = db_pre
-        return dX, None, dW if want_w else None, db, None, None, None, None, None
+        return dX, None, dW if want_w else None, db, None, None, None, None, None, None
 
 
 def graph_conv_fwd_train(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu: bool = False,
-                         out: torch.Tensor = None, Z: torch.Tensor = None):
+                         out: torch.Tensor = None, Z: torch.Tensor = None, z_dtype=None):
     """(out, Z) of one GraphConv layer through grl_graphconv_fwd_train: the
     one-kernel path writes Z as a by-product (for the backward's dW); the
     result is bitwise spmm_forward then linear_fwd.  out / Z: contiguous
@@ -841,8 +895,20 @@ def graph_conv_fwd_train(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=
     (grl_graphconv_fwd_train_bf16): out and Z bitwise the call's on X.float().
     With a bfloat16 X, out may be bfloat16 (_forward_args; a column-slice view
     is written in place, grl_graphconv_fwd_train_bf16_to_bf16): the fp32 out
-    rounded to nearest even in the kernel's epilogue, Z fp32 as before."""
-    X2, F, Wc, bc, out, Z = _forward_args("graph_conv_fwd_train", X, graph, W, b, out, Z, want_Z=True)
+    rounded to nearest even in the kernel's epilogue, Z fp32 as before.
+    z_dtype=torch.bfloat16, or a bfloat16 Z passed in (a bfloat16 X and a
+    bfloat16 out only; Z contiguous [num_rows, segments * F]): Z holds bf16 as
+    well (grl_graphconv_fwd_train_bf16_z16), bitwise the fp32 Z rounded to
+    nearest even -- half the bytes kept for the backward, which
+    linear_bwd_weight_bf16z reads as stored; out is bitwise the fp32-Z call's."""
+    who = "graph_conv_fwd_train"
+    if z_dtype not in (None, torch.float32, torch.bfloat16):
+        raise _lib.GrlError(f"{who}: z_dtype must be None, float32 or bfloat16 (got {z_dtype})")
+    if z_dtype == torch.bfloat16 or (Z is not None and Z.dtype == torch.bfloat16):
+        if z_dtype == torch.float32:
+            raise _lib.GrlError(f"{who}: z_dtype=float32 with a bfloat16 Z")
+        return _graph_conv_fwd_train_z16(who, X, graph, W, b, relu, out, Z)
+    X2, F, Wc, bc, out, Z = _forward_args(who, X, graph, W, b, out, Z, want_Z=True)
     K, C = Wc.shape
     csr = graph.csr_c(F)
     ws_bytes = _lib.lib().grl_linear_fwd_ex_workspace_size(graph.num_rows, K, C, graph.path_rows)
@@ -856,6 +922,41 @@ def graph_conv_fwd_train(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=
             ws_bytes += (graph.num_rows * C * 4 + 255) // 256 * 256
     ws = _workspace(ws_bytes, X.device)
     call("grl_graphconv_fwd_train" + sfx, *args, Z.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes,
+         current_stream_handle(X.device))
+    return out, Z
+
+
+def _graph_conv_fwd_train_z16(who: str, X, graph, W, b, relu: bool, out, Z):
+    """graph_conv_fwd_train with a bfloat16 Z (grl_graphconv_fwd_train_bf16_z16):
+    a bfloat16 X and a bfloat16 out (given, or a new contiguous one) on a
+    TypedGraph; Z the contiguous bfloat16 [num_rows, segments * F] tensor given
+    or a new one.  The workspace is the entry's own query: W's planes for the
+    one kernel, else the fp32 Z scratch, the linear's fp32 output and its
+    workspace."""
+    if isinstance(graph, EdgeBlockedGraph):
+        raise _lib.GrlError(f"{who}: a bfloat16 Z needs a TypedGraph (an EdgeBlockedGraph aggregates by blocks, in fp32)")
+    if X.dtype != torch.bfloat16:
+        raise _lib.GrlError(f"{who}: a bfloat16 Z needs bfloat16 node features (got {X.dtype}): there is no fp32-table "
+                            "form with a bf16 Z -- cast the table once")
+    if out is not None and out.dtype != torch.bfloat16:
+        raise _lib.GrlError(f"{who}: a bfloat16 Z needs a bfloat16 out (got {out.dtype}): the fp32-output entries keep "
+                            "an fp32 Z, whose gradient is fp32 too")
+    if out is None:
+        out = torch.empty(graph.num_rows, W.shape[1], dtype=torch.bfloat16, device=X.device)
+    X2, F, Wc, bc, out, _ = _forward_args(who, X, graph, W, b, out)
+    K, C = Wc.shape
+    if Z is None:
+        Z = torch.empty(graph.num_rows, K, dtype=torch.bfloat16, device=X.device)
+    elif (tuple(Z.shape) != (graph.num_rows, K) or Z.dtype != torch.bfloat16 or not Z.is_contiguous()
+          or Z.device != X.device):
+        raise _lib.GrlError(f"{who}: Z must be a contiguous bfloat16 {(graph.num_rows, K)} tensor on {X.device}")
+    csr = graph.csr_c(F)
+    ws_bytes = _lib.lib().grl_graphconv_fwd_train_bf16_z16_workspace_query(
+        ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), C, out.data_ptr(), out.stride(0),
+        Z.data_ptr())
+    ws = _workspace(ws_bytes, X.device)
+    call("grl_graphconv_fwd_train_bf16_z16", ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc),
+         C, int(relu), out.data_ptr(), out.stride(0), Z.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes,
          current_stream_handle(X.device))
     return out, Z
 
@@ -901,7 +1002,7 @@ RECOMPUTE_Z_BYTES = 8 << 30
 
 
 def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu: bool = False,
-               recompute: bool = None, out_dtype=None, fdrop=None, row0: int = 0) -> torch.Tensor:
+               recompute: bool = None, out_dtype=None, fdrop=None, row0: int = 0, z_dtype=None) -> torch.Tensor:
     """GraphConv forward (aggregation + linear [+ReLU]) as one autograd node;
     X: [num_cols, F] (or [B, N, F] for a batch graph).  When no gradient is
     wanted (eval, torch.no_grad) it is one grl_graphconv_fwd call instead:
@@ -958,7 +1059,21 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
     the unfused chain feature_dropout(graph_conv(...), fdrop, row0).  With
     gradients disabled it is graph_conv_infer followed by the in-place pass.
     In every other combination (an fp32 output, no ReLU, an EdgeBlockedGraph)
-    fdrop is applied as a separate feature_dropout after the node."""
+    fdrop is applied as a separate feature_dropout after the node.
+    z_dtype=torch.bfloat16 (with out_dtype=torch.bfloat16 on a TypedGraph only;
+    None and torch.float32: the fp32 Z as ever): the Z kept between the passes
+    holds bf16 (grl_graphconv_fwd_train_bf16_z16: the fp32 Z rounded to nearest
+    even as it is written), half the bytes -- the saved-activation precision
+    of mixed-precision training.  out, X.grad and db are bitwise those of
+    z_dtype=None (the multiply consumes the unrounded Z, and neither the data
+    gradient nor db reads Z); dW alone sees the rounded Z: where
+    grl_linear_bwd_weight_bf16zg applies (from PREMASK_ROWS rows or without a
+    ReLU; a nonzero workspace query, the dw_bf16z path option on) it is one
+    plane product on the two bf16 tables as stored, elsewhere Z is widened once
+    and the backward above runs on it -- the same dW bits either way where a
+    split-bf16 kernel runs.  recompute=None counts the bytes Z would take, 2 an
+    element; with recompute=True z_dtype has no effect (X is what is kept, and
+    the backward re-aggregates an fp32 Z).  Ignored when no gradient is wanted."""
     if X.dtype not in _TABLE_DTYPES:
         raise _lib.GrlError(f"graph_conv: node features must be float32 or bfloat16 (got {X.dtype})")
     if W.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
@@ -969,6 +1084,12 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
     if out_bf16 and (X.dtype != torch.bfloat16 or isinstance(graph, EdgeBlockedGraph)):
         raise _lib.GrlError(f"graph_conv: out_dtype=bfloat16 needs bfloat16 node features on a TypedGraph (got "
                             f"{X.dtype}): there is no fp32-table form with a bf16 output -- cast the table once")
+    if z_dtype not in (None, torch.float32, torch.bfloat16):
+        raise _lib.GrlError(f"graph_conv: z_dtype must be None, float32 or bfloat16 (got {z_dtype})")
+    z_bf16 = z_dtype == torch.bfloat16
+    if z_bf16 and not out_bf16:
+        raise _lib.GrlError("graph_conv: z_dtype=bfloat16 needs out_dtype=bfloat16 (bfloat16 node features on a "
+                            "TypedGraph): the fp32-output layer keeps an fp32 Z")
     fused = fdrop is not None and relu and out_bf16
     if not (torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (X, W, b))):
         if isinstance(graph, EdgeBlockedGraph):  # one int32 CSR per call: aggregate by blocks, then the linear
@@ -980,8 +1101,9 @@ def graph_conv(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None, relu
             return feature_dropout_apply(out, fdrop, int(row0), out=out)
         return out if fdrop is None else feature_dropout(out, fdrop, row0)
     if recompute is None:
-        recompute = graph.num_rows * graph.segments * X.shape[-1] * 4 > RECOMPUTE_Z_BYTES
-    out = _GraphConv.apply(X, graph, W, b, relu, bool(recompute), out_bf16, fdrop if fused else None, int(row0))
+        recompute = graph.num_rows * graph.segments * X.shape[-1] * (2 if z_bf16 else 4) > RECOMPUTE_Z_BYTES
+    out = _GraphConv.apply(X, graph, W, b, relu, bool(recompute), out_bf16, fdrop if fused else None, int(row0),
+                           z_bf16)
     return out if fused or fdrop is None else feature_dropout(out, fdrop, row0)
 
 

@@ -501,6 +501,38 @@ int grl_graphconv_fwd_train_bf16_to_bf16(
     int64_t ldo, float* Z, const GrlDropEdge* de, void* workspace,
     size_t workspace_bytes, grl_stream_t stream);
 
+/* grl_graphconv_fwd_train_bf16_to_bf16 whose Z holds bf16 bits as well: Z
+ * [num_rows, K] contiguous, K = (has_self + num_types) * F, half the bytes
+ * kept for the weight gradient (grl_linear_bwd_weight_bf16zg reads it as
+ * stored).
+ *   out is BITWISE grl_graphconv_fwd_train_bf16_to_bf16's;
+ *   Z is BITWISE the round-to-nearest-even bf16 of the fp32 Z that entry
+ *   writes (the multiply consumes the unrounded rows; only the copy that
+ *   goes to memory is rounded, once).
+ * One kernel where that entry takes its one kernel AND Z is 8 B-aligned (its
+ * gather waves store 8 B of a row at a time; K % 4 == 0 holds whenever the
+ * one-kernel shape rule does); the query then answers the size of W's planes.
+ * Elsewhere grl_typed_spmm_fwd_bf16 into an fp32 Z scratch at the head of the
+ * workspace, grl_linear_fwd_ex with g->path_rows into an fp32 [num_rows, C]
+ * scratch behind it, and the rounding pass over each -- the same bits; the
+ * query answers that total (roundup(num_rows * K * 4, 256) + roundup(num_rows
+ * * C * 4, 256) + grl_linear_fwd_ex_workspace_size(num_rows, K, C,
+ * g->path_rows)).  A smaller workspace: GRL_E_WORKSPACE.  graphconv_fused = 0
+ * forces that form.
+ * GRL_E_INVALID, decided on the host: the sibling entry's checks, plus a NULL
+ * or odd Z (the query answers 0 for ldo < C).  num_rows == 0: GRL_OK.  A
+ * bounded wait that runs out fills out's C columns of every row AND Z with
+ * bf16 NaN and is reported by grl_check() under this entry's name.          */
+size_t grl_graphconv_fwd_train_bf16_z16_workspace_query(
+    const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+    const float* W, int32_t C, const uint16_t* out, int64_t ldo,
+    const uint16_t* Z);
+int grl_graphconv_fwd_train_bf16_z16(
+    const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+    const float* W, const float* bias, int32_t C, int32_t relu, uint16_t* out,
+    int64_t ldo, uint16_t* Z, const GrlDropEdge* de, void* workspace,
+    size_t workspace_bytes, grl_stream_t stream);
+
 /* Data gradient of one GraphConv layer in ONE kernel.  Replaces the
  * autograd chain MmBackward0 (dZ = G W^T, robust_gcn.py:50) then
  * BmmBackward0 (dX = A_drop^T dZ, robust_gcn.py:45) by its reassociation
@@ -638,6 +670,34 @@ int grl_linear_bwd_weight_bf16g(const float* Z, int64_t ldz, const uint16_t* g,
                                 int64_t ldg, float* dW, float* db, int64_t M,
                                 int32_t K, int32_t C, void* workspace,
                                 size_t workspace_bytes, grl_stream_t stream);
+
+/* grl_linear_bwd_weight_bf16g for a Z stored as bf16 too (bf16 bits, [M, K],
+ * rows ldz >= K elements apart; grl_graphconv_fwd_train_bf16_z16 writes one):
+ *   dW = Z^T g   [K, C] contiguous        db = sum over rows of g   [C] or NULL
+ * Both operands are ONE plane of the split-bf16 scheme, so the kernel
+ * (gemm_x1t_kernel) issues one plane product per block where the bf16g entry
+ * issues three, two of them on planes that are all zeros; it runs over the
+ * same K16 steps, splits and slab order, and db is that entry's.  dW and db are
+ * bitwise grl_linear_bwd_weight_bf16g(widened Z, g), and so bitwise
+ * grl_linear_bwd_weight(widened Z, widened g, NULL), for finite operands (-0
+ * included; NaN and Inf are outside the contract).
+ * Eligible -- the query answers grl_linear_bwd_weight_workspace_size(M, K, C),
+ * else 0 -- where grl_linear_bwd_weight would take its split-bf16 kernel
+ * (gemm_x6 on, M >= 16, K % 4 == 0, C % 4 == 0, 2 M K C >= 1.6e10), Z and g
+ * are 8 B-aligned with ldz % 4 == 0 and ldg % 4 == 0, and the path option
+ * dw_bf16z is 1.  Anything else: GRL_E_UNSUPPORTED -- there is no second path
+ * inside the library; the caller widens Z.  GRL_E_INVALID, decided on the
+ * host: a negative size, ldz < K, ldg < C, an odd Z or g address, a NULL Z, g
+ * or dW with M > 0.  A missing or short workspace: GRL_E_WORKSPACE.  M == 0
+ * writes dW = 0 and db = 0; K == 0 or C == 0 returns GRL_OK.  Stream-ordered,
+ * no host sync.                                                             */
+size_t grl_linear_bwd_weight_bf16zg_workspace_query(const uint16_t* Z, int64_t ldz,
+                                                    const uint16_t* g, int64_t ldg,
+                                                    int64_t M, int32_t K, int32_t C);
+int grl_linear_bwd_weight_bf16zg(const uint16_t* Z, int64_t ldz, const uint16_t* g,
+                                 int64_t ldg, float* dW, float* db, int64_t M,
+                                 int32_t K, int32_t C, void* workspace,
+                                 size_t workspace_bytes, grl_stream_t stream);
 
 /* ReLU's derivative applied once (autograd ThresholdBackward of the ReLU at
  * drop_robust_gcn.py:76, the bias gradient of robust_gcn.py:51 with it):

@@ -54,6 +54,18 @@ KERNELS_DW_BF16G = [
      "linear_bwd_weight_bf16g_c3.json)"),
 ]
 
+# the bf16-Z training forward and its dW (tests/test_codegen_pin_z16.py; profiles/train_z16_c3.json)
+PINS_Z16 = os.path.join(ROOT, "tests", "golden", "codegen_pins_z16.json")
+KERNELS_Z16 = [
+    ("graphconv.hip", "_ZN3grl12_GLOBAL__N_126graphconv_ws_bf16oz_kernelILi16ELb0ELi1ELi8EEE",
+     "one-kernel GraphConv training forward at F=256 writing a bf16 out and a bf16 Z "
+     "(grl_graphconv_fwd_train_bf16_z16)"),
+    ("graphconv.hip", "_ZN3grl12_GLOBAL__N_126graphconv_ws_bf16oz_kernelILi16ELb0ELi2ELi8EEE",
+     "the same at F=512, C<=256 (gcn3 at d=256)"),
+    ("linear.hip", "_ZN3grl12_GLOBAL__N_115gemm_x1t_kernelILi2EEE",
+     "dW from a bf16 Z and a bf16 gradient, split-K slabs (grl_linear_bwd_weight_bf16zg at C3)"),
+]
+
 
 def kernel_stream(asm: str, prefix: str):
     m = re.search(r"^(" + re.escape(prefix) + r"[^:\s]*):", asm, re.M)
@@ -132,7 +144,7 @@ if __name__ == "__main__":
         root = sys.argv[sys.argv.index("--root") + 1] if "--root" in sys.argv else ROOT
         print(json.dumps(compute_all(os.path.abspath(root)), indent=1, sort_keys=True))
         sys.exit(0)
-    for path, kernels in ((PINS, KERNELS), (PINS_DW_BF16G, KERNELS_DW_BF16G)):
+    for path, kernels in ((PINS, KERNELS), (PINS_DW_BF16G, KERNELS_DW_BF16G), (PINS_Z16, KERNELS_Z16)):
         pins = compute(kernels)
         if "--write" in sys.argv:
             with open(path, "w") as f:
