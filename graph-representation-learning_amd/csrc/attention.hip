@@ -559,10 +559,11 @@ __global__ void attn_split_rows_kernel(const float* __restrict__ src, int64_t ro
 // is its destination.  Rows past N re-read row N-1 (finite values whose
 // scores / probabilities the kernels mask to zero).  Completion: the
 // caller's vmcnt(0) + barrier at the top of the block that reads it.
-template <int W, int LAYOUT, int NW = 4>
+// NP planes (3; 1 = a table stored as bf16, which is its own plane 0).
+template <int W, int LAYOUT, int NW = 4, int NP = 3>
 __device__ __forceinline__ void dma_block(const uint16_t* planes, int64_t ps, int64_t r0, int64_t N, uint16_t* lds,
                                           int wave, int lane) {
-  constexpr int PL = 32 * W, NI = 3 * PL / 512;  // 1 KB chunks, dealt to the NW waves of the workgroup
+  constexpr int PL = 32 * W, NI = NP * PL / 512;  // 1 KB chunks, dealt to the NW waves of the workgroup
   const int ln = lane;
 #pragma unroll
   for (int j = 0; j < (NI + NW - 1) / NW; ++j) {
@@ -580,9 +581,9 @@ __device__ __forceinline__ void dma_block(const uint16_t* planes, int64_t ps, in
 // dma_block with this lane's chunk addresses computed once: per block only a
 // uniform row offset is added (the last, partial block takes dma_block's
 // clamped path).  Costs 2 VGPRs per chunk slot (the forward has the room).
-template <int W, int LAYOUT, int NW = 4>
+template <int W, int LAYOUT, int NW = 4, int NP = 3>
 struct DmaRows {
-  static constexpr int PL = 32 * W, NI = 3 * PL / 512, NJ = (NI + NW - 1) / NW;
+  static constexpr int PL = 32 * W, NI = NP * PL / 512, NJ = (NI + NW - 1) / NW;
   const uint16_t* planes;
   const uint16_t* src[NJ];
   int64_t ps;
@@ -606,7 +607,7 @@ struct DmaRows {
         if (i < NI) dma16(src[j] + r0 * W, lds + i * 512);
       }
     } else {
-      dma_block<W, LAYOUT, NW>(planes, ps, r0, N, lds, wave, lane);
+      dma_block<W, LAYOUT, NW, NP>(planes, ps, r0, N, lds, wave, lane);
     }
   }
 };
@@ -1114,6 +1115,326 @@ __global__ __launch_bounds__(64 * NW) void attn_fwd_x6p_kernel(AttnArgs a) {
     if (h == 0 && a.rmax) {
       a.rmax[b * N + q] = m * ALN2;  // natural-log row max (the saved-stat contract)
       a.rsum[b * N + q] = l;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------
+// attn_fwd_x6p_kernel over K and H tables STORED as bf16 (a.Kpl [B, N, DKP],
+// a.Hpl [B, N, DV]: the caller's tables, staged as they lie -- a bf16 value is
+// plane 0 of its split, planes 1 and 2 are +0).  K and H are the A operands of
+// both products, so each MFMA6 becomes x3a_mfma: a 32-key block is 3 KC + 6 NT
+// MFMAs instead of 6 KC + 12 NT, an LDS stage holds one plane, the DMA moves a
+// third of the bytes, and no split pass or plane workspace precedes the call.
+// Q (scaled by log2 e) and P stay three planes.  Everything that fixes a bit
+// is attn_fwd_x6p_kernel's: the order of max / 2^x / row sum, the rescale
+// skip, the partial-block mask, the key split's partials, the epilogue.  The
+// score accumulator starts at +0 in every block, so m and l (row_max,
+// row_sum) are bitwise that kernel's on the widened tables; o can be -0 after
+// a rescale that underflowed, which the skipped zero-plane products would
+// have turned into +0: out and o_norm are equal as values, a zero's sign
+// apart (x3a_mfma).
+// The interleave (a schedule, not a contract): block it's P.H runs in groups
+// of one (t, u) product, 3 MFMAs, block it+1's softmax in 7 pieces after
+// groups 1 .. last, as in attn_fwd_x6p_kernel (groups of two products were
+// measured and decided nothing: DESIGN.md §4.22).
+template <int DKP, int NT, bool SPLIT, int NW = 4>
+__global__ __launch_bounds__(64 * NW) void attn_fwd_x3p_kernel(AttnArgs a) {
+  constexpr int DV = NT * 32, KC = DKP / 16;
+  constexpr int KPL = 32 * DKP, HPL = 32 * DV;  // bf16 per plane
+  constexpr int KST = KPL, HST = HPL;           // one stage: the one plane
+  // B2 as in attn_fwd_x6p_kernel: one barrier per two key blocks, four H and
+  // four K stages (36 KB of LDS at dv = 128)
+  constexpr bool B2 = GRL_ATTN_B2 && NW == 8 && NT <= 4;
+  __shared__ __attribute__((aligned(16))) uint16_t Kp_s[(B2 ? 4 : 3) * KST];
+  __shared__ __attribute__((aligned(16))) uint16_t Hp_s[(B2 ? 4 : 2) * HST];
+  auto hstage = [](int j) { return B2 ? (j & 3) : (j & 1); };
+  auto kstage = [](int j) { return B2 ? (j & 3) : (j % 3); };
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l32 = lane & 31, h = lane >> 5;
+  const int64_t N = a.N, b = blockIdx.y;
+  const float* Qb = a.Q + b * N * a.dk;
+  const int64_t q = a.q0 + (int64_t)blockIdx.x * (32 * NW) + wave * 32 + l32;
+  const int64_t k_lo = SPLIT ? (int64_t)blockIdx.z * a.kr : 0, k_hi = SPLIT ? min<int64_t>(N, k_lo + a.kr) : N;
+  const int nblk = (int)((k_hi - k_lo + 31) >> 5);
+  const bool partial = ((k_hi - k_lo) & 31) != 0;
+
+  bf16x8_t qp[KC][3];
+#pragma unroll
+  for (int kc = 0; kc < KC; ++kc) {
+    float v[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int d = kc * 16 + 8 * h + j;
+      v[j] = (q < a.q1 && d < a.dk) ? Qb[q * a.dk + d] * ALOG2E : 0.0f;  // base-2 scores
+    }
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), qp[kc][0], qp[kc][1],
+            qp[kc][2]);
+  }
+  f32x16 o[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) o[t] = zero16();
+  float m = -INFINITY, l = 0.0f;
+  DmaRows<DKP, PL_PLAIN, NW, 1> kd;
+  DmaRows<DV, PL_HSWZ, NW, 1> hd;
+  kd.init(a.Kpl + b * N * DKP, 0, wave, lane);
+  hd.init(a.Hpl + b * N * DV, 0, wave, lane);
+  kd.issue(k_lo, N, Kp_s, wave, lane);
+  hd.issue(k_lo, N, Hp_s, wave, lane);
+  if (nblk > 1) kd.issue(k_lo + 32, N, Kp_s + KST, wave, lane);
+  if (B2 && nblk > 1) hd.issue(k_lo + 32, N, Hp_s + HST, wave, lane);  // the first pair's H and
+  if (B2 && nblk > 2) kd.issue(k_lo + 64, N, Kp_s + 2 * KST, wave, lane);  // K(2), before its barrier
+  const int trq = (lane & 15) >> 2;
+  const int trc = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+
+  // S^T = K Q^T of the block staged at Kp (base 2)
+  auto scores = [&](const uint16_t* Kp) {
+    f32x16 sc = zero16();
+#pragma unroll
+    for (int kc = 0; kc < KC; ++kc) {
+      const int off = l32 * DKP + kc * 16 + 8 * h;
+      x3a_mfma(sc, *reinterpret_cast<const bf16x8_t*>(&Kp[off]), qp[kc]);
+    }
+    return sc;
+  };
+  // online softmax of one block: updates m, l; P -> planes; returns alpha
+  auto softmax = [&](f32x16& sc, bf16x8_t (&pp)[2][3]) {
+    float mx = fmaxf(sc[0], sc[1]);
+#pragma unroll
+    for (int r = 2; r < 16; r += 2) mx = fmaxf(fmaxf(mx, sc[r]), sc[r + 1]);
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    const float mn = fmaxf(m, mx);
+    const float alpha = aexp2(m - mn);
+    float ps = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      sc[r] = aexp2(sc[r] - mn);
+      ps += sc[r];
+    }
+    ps += __shfl_xor(ps, 32);
+    l = l * alpha + ps;
+    m = mn;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+      split8(make_float4(sc[8 * u], sc[8 * u + 1], sc[8 * u + 2], sc[8 * u + 3]),
+              make_float4(sc[8 * u + 4], sc[8 * u + 5], sc[8 * u + 6], sc[8 * u + 7]), pp[u][0], pp[u][1],
+              pp[u][2]);
+    return alpha;
+  };
+  auto mask = [&](f32x16& sc, int64_t k0) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+      if (k0 + kappa(r, h) >= k_hi) sc[r] = -INFINITY;
+  };
+  // O^T += H^T P^T of the block staged at Hp
+  auto pv = [&](const uint16_t* Hp, const bf16x8_t (&pp)[2][3]) {
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int key0 = kappa(8 * u + trq, h), key1 = kappa(8 * u + 4 + trq, h);
+        x3a_mfma(o[t], tr8(&Hp[hswz<DV>(key0, t * 32 + trc)], &Hp[hswz<DV>(key1, t * 32 + trc)]), pp[u]);
+      }
+  };
+  auto rescale = [&](float alpha) {
+    if (__any(alpha != 1.0f)) {  // wave-uniform; x * 1 == x, so skipping is exact
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) o[t][r] *= alpha;
+    }
+  };
+
+  // prologue: block 0's scores and softmax (o is zero: no rescale)
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  bf16x8_t pp[2][3];
+  {
+    f32x16 sc = scores(Kp_s);
+    if (nblk == 1 && partial) mask(sc, k_lo);
+    softmax(sc, pp);
+  }
+  float alpha = 1.0f;
+  // iteration it: block it's P.H with block it+1's softmax in the same body
+  // (hs: the H stage as a constant, -1 = at run time: attn_fwd_x6p_kernel)
+  auto iteration = [&](int it, auto masked, auto hs) {
+    constexpr bool MASK = decltype(masked)::value;
+    constexpr int HS = decltype(hs)::value;
+    const int64_t k0 = k_lo + 32 * (int64_t)it;
+    if constexpr (B2) {
+      // even it: blocks it, it+1's H and K(it+1), K(it+2) landed; every wave is
+      // done with blocks it-2, it-1, whose stages the next pair's DMAs take
+      if ((HS >= 0 ? HS : it) % 2 == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (it + 2 < nblk) hd.issue(k0 + 64, N, Hp_s + hstage(it + 2) * HST, wave, lane);
+        if (it + 3 < nblk) hd.issue(k0 + 96, N, Hp_s + hstage(it + 3) * HST, wave, lane);
+        if (it + 3 < nblk) kd.issue(k0 + 96, N, Kp_s + kstage(it + 3) * KST, wave, lane);
+        if (it + 4 < nblk) kd.issue(k0 + 128, N, Kp_s + kstage(it + 4) * KST, wave, lane);
+      }
+    } else {
+      // block it's H and block it+1's K landed; every wave is done with the
+      // stages the next DMAs overwrite (H of block it-1, K of block it-1)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      if (it + 1 < nblk) hd.issue(k0 + 32, N, Hp_s + hstage(it + 1) * HST, wave, lane);
+      if (it + 2 < nblk) kd.issue(k0 + 64, N, Kp_s + kstage(it + 2) * KST, wave, lane);
+    }
+    rescale(alpha);
+    f32x16 sc = scores(Kp_s + (B2 && HS >= 0 ? (HS + 1) & 3 : kstage(it + 1)) * KST);
+    if constexpr (MASK) mask(sc, k0 + 32);
+    bf16x8_t pn[2][3];
+    // block it's P.H in 2 NT groups of 3 MFMAs; block it+1's softmax cut into
+    // 7 pieces placed after groups 1 .. 2 NT - 1 (group 0 covers the score
+    // MFMAs' latency), each group fenced so its VALU fills that group's gaps
+    const lds_u16* Hp = (const lds_u16*)Hp_s + (HS < 0 ? hstage(it) : HS) * HST;
+    float mn = 0.0f, an = 1.0f, ps = 0.0f;
+    auto piece = [&](int pc) {
+      if (pc == 0) {
+        float mx = fmaxf(sc[0], sc[1]);
+#pragma unroll
+        for (int r = 2; r < 16; r += 2) mx = fmaxf(fmaxf(mx, sc[r]), sc[r + 1]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32));
+        mn = fmaxf(m, mx);
+        an = aexp2(m - mn);
+      } else if (pc <= 2) {
+#pragma unroll
+        for (int r = 8 * (pc - 1); r < 8 * pc; ++r) {
+          sc[r] = aexp2(sc[r] - mn);
+          ps += sc[r];
+        }
+        if (pc == 2) {
+          ps += __shfl_xor(ps, 32);
+          l = l * an + ps;
+          m = mn;
+        }
+      } else {
+        const int u = (pc - 3) >> 1, half = (pc - 3) & 1;
+        if (half == 0) {
+          uint2 l0, l1, l2;
+          split3(make_float4(sc[8 * u], sc[8 * u + 1], sc[8 * u + 2], sc[8 * u + 3]), l0, l1, l2);
+          pn[u][0] = __builtin_bit_cast(bf16x8_t, make_uint4(l0.x, l0.y, 0u, 0u));
+          pn[u][1] = __builtin_bit_cast(bf16x8_t, make_uint4(l1.x, l1.y, 0u, 0u));
+          pn[u][2] = __builtin_bit_cast(bf16x8_t, make_uint4(l2.x, l2.y, 0u, 0u));
+        } else {
+          uint2 h0, h1, h2;
+          split3(make_float4(sc[8 * u + 4], sc[8 * u + 5], sc[8 * u + 6], sc[8 * u + 7]), h0, h1, h2);
+          uint4 w0 = __builtin_bit_cast(uint4, pn[u][0]), w1 = __builtin_bit_cast(uint4, pn[u][1]),
+                w2 = __builtin_bit_cast(uint4, pn[u][2]);
+          pn[u][0] = __builtin_bit_cast(bf16x8_t, make_uint4(w0.x, w0.y, h0.x, h0.y));
+          pn[u][1] = __builtin_bit_cast(bf16x8_t, make_uint4(w1.x, w1.y, h1.x, h1.y));
+          pn[u][2] = __builtin_bit_cast(bf16x8_t, make_uint4(w2.x, w2.y, h2.x, h2.y));
+        }
+      }
+    };
+    // group g's H fragment (one plane, transposed reads)
+    auto load_h = [&](int g) {
+      const int t = g >> 1, u = g & 1;
+      const int key0 = kappa(8 * u + trq, h), key1 = kappa(8 * u + 4 + trq, h);
+      return tr8s(Hp + hswz<DV>(key0, t * 32 + trc), Hp + hswz<DV>(key1, t * 32 + trc));
+    };
+    // HPF: the next group's fragment is read one group ahead (two register
+    // sets of 4 VGPRs: every NT <= 4 instance has the room, so without
+    // attn_fwd_x6p_kernel's DKP / NW condition)
+    constexpr bool HPF = GRL_ATTN_HPF && NT <= 4;
+    bf16x8_t hq[HPF ? 2 : 1];
+    if constexpr (HPF) hq[0] = load_h(0);
+    (void)hq;
+#pragma unroll
+    for (int g = 0; g < 2 * NT; ++g) {
+      if constexpr (HPF) {
+        if (g + 1 < 2 * NT) hq[(g + 1) & 1] = load_h(g + 1);
+      } else {
+        hq[0] = load_h(g);
+      }
+      x3a_mfma(o[g >> 1], hq[HPF ? g & 1 : 0], pp[g & 1]);
+      // pieces assigned to this group: piece pc runs after group 1 + pc * (2 NT - 1) / 7
+#pragma unroll
+      for (int pc = 0; pc < 7; ++pc)
+        if (g >= 1 && 1 + pc * (2 * NT - 1) / 7 == g) piece(pc);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    alpha = an;
+#pragma unroll
+    for (int u = 0; u < 2; ++u)
+#pragma unroll
+      for (int pl = 0; pl < 3; ++pl) {
+        // keep block it+1's split in this body (attn_fwd_x6p_kernel)
+        if constexpr (GRL_ATTN_PIN_PN && NT <= 4) asm volatile("" : "+v"(pn[u][pl]));
+        pp[u][pl] = pn[u][pl];
+      }
+  };
+  using HRun = std::integral_constant<int, -1>;
+  int it = 0;
+#if GRL_ATTN_HU2
+  // (dv = 256, NT = 8 keeps the rolled loop, as attn_fwd_x6p_kernel does)
+  if constexpr (NT > 4) {
+  } else if constexpr (B2) {
+    for (; it + 5 < nblk; it += 4) {  // it % 4 == 0: H stages 0..3
+      iteration(it, std::false_type{}, std::integral_constant<int, 0>{});
+      iteration(it + 1, std::false_type{}, std::integral_constant<int, 1>{});
+      iteration(it + 2, std::false_type{}, std::integral_constant<int, 2>{});
+      iteration(it + 3, std::false_type{}, std::integral_constant<int, 3>{});
+    }
+  } else {
+    for (; it + 3 < nblk; it += 2) {  // it even: H stages 0, 1
+      iteration(it, std::false_type{}, std::integral_constant<int, 0>{});
+      iteration(it + 1, std::false_type{}, std::integral_constant<int, 1>{});
+    }
+  }
+#endif
+  for (; it + 2 < nblk; ++it) iteration(it, std::false_type{}, HRun{});
+  if (it + 1 < nblk) {
+    // the last block's softmax, always through the MASK instantiation (on a full
+    // block the mask changes nothing): a second, unmasked copy of the body here
+    // made the dv = 256 8-wave form spill (440 B of scratch; one copy: 0 B)
+    iteration(it, std::true_type{}, HRun{});
+    ++it;
+  }
+  // the last block: its P.H only
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  rescale(alpha);
+  pv(Hp_s + hstage(it) * HST, pp);
+
+  // the epilogue's query and half-wave, formed again from the thread id behind an
+  // opaque copy: held across the loop they cost the dk = 32, dv = 256 8-wave
+  // form its last VGPR (an 8 B spill)
+  int tid_e = threadIdx.x;
+  asm volatile("" : "+v"(tid_e));
+  const int64_t qe = a.q0 + (int64_t)blockIdx.x * (32 * NW) + (tid_e >> 6) * 32 + (tid_e & 31);
+  const int he = (tid_e & 63) >> 5;
+  if (SPLIT && qe < a.q1) {  // key split: unnormalised partials, combined by attn_fwd_combine_kernel
+    const int64_t rows = (int64_t)gridDim.y * N, row = b * N + qe, zs = blockIdx.z;
+    float* po = a.part + zs * rows * a.dv + row * a.dv;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int f = t * 32 + kappa(r, he);
+        if (f < a.dv) po[f] = o[t][r];
+      }
+    if (he == 0) {
+      float* pm = a.part + (int64_t)gridDim.z * rows * a.dv;
+      pm[zs * rows + row] = m;
+      pm[((int64_t)gridDim.z + zs) * rows + row] = l;
+    }
+  } else if (qe < a.q1) {
+    const float inv = 1.0f / l;
+    const int64_t base = (b * N + qe) * a.dv;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int f = t * 32 + kappa(r, he);
+        if (f < a.dv) {
+          const float on = o[t][r] * inv;
+          a.out[base + f] = a.gamma[f] * on + a.V[base + f];
+          if (a.onorm) a.onorm[base + f] = on;
+        }
+      }
+    if (he == 0 && a.rmax) {
+      a.rmax[b * N + qe] = m * ALN2;  // natural-log row max (the saved-stat contract)
+      a.rsum[b * N + qe] = l;
     }
   }
 }
@@ -2370,6 +2691,48 @@ int dispatch(AttnPass pass, const AttnArgs& a, int64_t B, int S, hipStream_t st)
   return dispatch_nt<64>(pass, a, B, S, st);
 }
 
+// The forward over bf16 K / H tables (a.Kpl, a.Hpl: the tables themselves,
+// dk == DKP and dv == 32 NT): attn_fwd_x3p_kernel at every N (no split launch
+// to amortise, so no row threshold), 8-wave workgroups unless attn_fwd8 = 0.
+template <int DKP, int NT>
+int launch_attn_bf16kv(const AttnArgs& a0, int64_t B, int S, hipStream_t st) {
+  AttnArgs a = a0;
+  if (!a.part) S = 1;
+  if (S == 1) {
+    a.part = nullptr;
+    a.kr = a.N;
+  }
+  const int64_t nq = a.q1 - a.q0, rows = B * a.N;
+  if (attn_fwd8_enabled()) {  // 256 queries per workgroup
+    const dim3 g8((unsigned)ceil_div(nq, 256), (unsigned)B, (unsigned)S);
+    with_bool(S > 1, [&](auto s) {
+      hipLaunchKernelGGL((attn_fwd_x3p_kernel<DKP, NT, s(), 8>), g8, dim3(512), 0, st, a);
+    });
+  } else {
+    const dim3 grid((unsigned)ceil_div(nq, 128), (unsigned)B, (unsigned)S);
+    with_bool(S > 1, [&](auto s) {
+      hipLaunchKernelGGL((attn_fwd_x3p_kernel<DKP, NT, s()>), grid, dim3(256), 0, st, a);
+    });
+  }
+  if (S > 1) {
+    GRL_LAUNCH_CHECK();
+    const unsigned red = (unsigned)std::min<int64_t>(ceil_div(rows * a.dv, 256), 8192);
+    hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3(red), dim3(256), 0, st, a, rows, S);
+  }
+  GRL_LAUNCH_CHECK();
+  return GRL_OK;
+}
+
+template <int DKP>
+int dispatch_bf16kv_nt(const AttnArgs& a, int64_t B, int S, hipStream_t st) {
+  switch (a.dv / 32) {
+    case 1: return launch_attn_bf16kv<DKP, 1>(a, B, S, st);
+    case 2: return launch_attn_bf16kv<DKP, 2>(a, B, S, st);
+    case 4: return launch_attn_bf16kv<DKP, 4>(a, B, S, st);
+    default: return launch_attn_bf16kv<DKP, 8>(a, B, S, st);
+  }
+}
+
 constexpr int64_t kAttnPlaneMinRows = 4096;
 
 // Workspace of the PRE staging: bf16 planes [3][B*N][W] of K, H (forward and
@@ -2499,6 +2862,75 @@ extern "C" int grl_node_attention_fwd_rows(const float* Q, const float* K, const
     }
   }
   return dispatch(PASS_FWD, a, B, S, st);
+}
+
+// ---- forward over K / H tables stored as bf16 (grl.h) -----------------------
+extern "C" int32_t grl_node_attention_fwd_bf16kv_path(int64_t B, int64_t N, int32_t dk, int32_t dv) {
+  (void)B;
+  (void)N;
+  // the tables are staged as they lie: no padded width, and the x6 scheme chosen
+  const bool dk_ok = dk == 16 || dk == 32, dv_ok = dv == 32 || dv == 64 || dv == 128 || dv == 256;
+  return dk_ok && dv_ok && attn_x6_enabled() ? 1 : 0;
+}
+
+extern "C" size_t grl_node_attention_fwd_bf16kv_workspace_size(int64_t B, int64_t N, int32_t dk, int32_t dv) {
+  if (B <= 0 || N <= 0 || !grl_node_attention_fwd_bf16kv_path(B, N, dk, dv)) return 0;
+  int64_t kr;
+  const int S = attn_splits(B, N, &kr);  // the key split's (o, m, l) partials, nothing else
+  return S > 1 ? ((size_t)S * B * N * (dv + 2) * 4 + 255) / 256 * 256 + 512 : 0;
+}
+
+extern "C" int grl_node_attention_fwd_bf16kv_rows(const float* Q, const uint16_t* K16, const uint16_t* H16,
+                                                  const float* V, const float* gamma, float* out, float* o_norm,
+                                                  float* row_max, float* row_sum, int64_t B, int64_t N, int32_t dk,
+                                                  int32_t dv, int64_t q_begin, int64_t q_end, void* workspace,
+                                                  size_t workspace_bytes, grl_stream_t stream) {
+  TraceRange trace_("grl_node_attention_fwd_bf16kv");
+  int rc = check_dims("grl_node_attention_fwd_bf16kv", B, N, dk, dv);
+  if (rc) return rc;
+  GRL_CHECK_ARG(0 <= q_begin && q_begin <= q_end && q_end <= N, "grl_node_attention_fwd_bf16kv: query rows "
+                "[%lld, %lld) outside [0, %lld)", (long long)q_begin, (long long)q_end, (long long)N);
+  if (q_begin == q_end) return GRL_OK;
+  if (B == 0 || N == 0) return GRL_OK;
+  GRL_CHECK_ARG((dk == 0 || (Q && K16)) && H16 && V && gamma && out, "grl_node_attention_fwd_bf16kv: NULL pointer");
+  GRL_CHECK_ARG((row_max == nullptr) == (row_sum == nullptr),
+                "grl_node_attention_fwd_bf16kv: row_max/row_sum: both or none");
+  if (!grl_node_attention_fwd_bf16kv_path(B, N, dk, dv))
+    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_node_attention_fwd_bf16kv: dk %d, dv %d (attn_x6 %d): widen K and H and call "
+             "grl_node_attention_fwd_rows", dk, dv, (int)attn_x6_enabled());
+  if ((reinterpret_cast<uintptr_t>(K16) | reinterpret_cast<uintptr_t>(H16)) & 15)
+    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_node_attention_fwd_bf16kv: K16 / H16 not 16 B-aligned: widen them and call "
+             "grl_node_attention_fwd_rows");
+  AttnArgs a{};
+  a.Q = Q;
+  a.Kpl = K16;
+  a.Hpl = H16;
+  a.V = V;
+  a.gamma = gamma;
+  a.out = out;
+  a.onorm = o_norm;
+  a.rmax = row_max;
+  a.rsum = row_sum;
+  a.N = N;
+  a.dk = dk;
+  a.dv = dv;
+  a.q0 = q_begin;
+  a.q1 = q_end;
+  int S = 1;
+  if (workspace) {  // the key split of grl_node_attention_fwd_rows: S depends on (B, N) alone
+    unsigned char* cur = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    const unsigned char* end = static_cast<unsigned char*>(workspace) + workspace_bytes;
+    int64_t kr;
+    S = attn_splits(B, N, &kr);
+    if (S > 1 && cur + (size_t)S * B * N * (dv + 2) * 4 <= end) {
+      a.part = reinterpret_cast<float*>(cur);
+      a.kr = kr;
+    } else {
+      S = 1;
+    }
+  }
+  hipStream_t st = as_stream(stream);
+  return dk == 16 ? dispatch_bf16kv_nt<16>(a, B, S, st) : dispatch_bf16kv_nt<32>(a, B, S, st);
 }
 
 extern "C" int grl_node_attention_bwd_rows(const float* Q, const float* K, const float* H, const float* dO,

@@ -110,6 +110,24 @@ __device__ __forceinline__ void x3_mfma(f32x16& acc, const bf16x8_t (&a)[3], bf1
   mfma_bf16(acc, a[0], b);
 }
 
+// acc += a b for an a that is ONE bf16 plane (values stored as bf16:
+// a1 = a2 = 0) and a split b: x6_mfma's sequence without its three products
+// on a zero plane (a2 b0, a1 b1, a1 b0), leaving a b2, a b1, a b0 in that
+// order.  The MFMA's operand positions are not interchangeable, so this is
+// not x3_mfma with its arguments swapped.  The skipped products add sums of
+// +-0 to the accumulator: x + (+-0) = x for x != 0 and +0 + (+-0) = +0 under
+// round to nearest, so an accumulator that starts at +0 (never -0 afterwards)
+// gets x6_mfma's bits on the widened a (DESIGN.md §4.19's argument).  An
+// accumulator that can hold -0 when the call begins (the attention forward's
+// o after an alpha rescale that underflowed) keeps it here where x6_mfma's
+// first zero product turns it into +0: equal values, a zero's sign apart
+// (DESIGN.md §4.22).
+__device__ __forceinline__ void x3a_mfma(f32x16& acc, bf16x8_t a, const bf16x8_t (&b)[3]) {
+  mfma_bf16(acc, a, b[2]);
+  mfma_bf16(acc, a, b[1]);
+  mfma_bf16(acc, a, b[0]);
+}
+
 // acc += a b for an a and a b that are each ONE bf16 plane (both stored as
 // bf16): the single product a0 b.  It is bitwise x3_mfma on an a whose planes
 // 1 and 2 are +0 (what split3 gives for a value that is a bf16 already: both

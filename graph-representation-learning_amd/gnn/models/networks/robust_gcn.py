@@ -181,6 +181,10 @@ class NodeSelfAtten(nn.Module):
         self.softmax = nn.Softmax(-1)
         self.gamma = nn.Parameter(torch.empty(input_dim))
         nn.init.normal_(self.gamma)
+        # torch.bfloat16 (set after construction, like GraphCNNDropEdge.activation_dtype): on the
+        # libgrl path of an unsharded graph the keys g and values h go to the attention core as
+        # bf16 tables.  None, a shard, the torch path and the CPU: today's fp32 path, bit for bit.
+        self.kv_dtype = None
 
     def forward(self, V: torch.Tensor, shard=None) -> torch.Tensor:
         """shard (additive): the grl.dist.ShardedGraph whose rows V holds --
@@ -196,6 +200,10 @@ class NodeSelfAtten(nn.Module):
             fgh = linear_rows(V, W, b, True, pr)
             dk = self.f[0].out_features
             f, g, h = fgh[..., :dk], fgh[..., dk:2 * dk], fgh[..., 2 * dk:]
+            if self.kv_dtype == torch.bfloat16 and shard is None:
+                # key / value tables stored as bf16: rounded once (N x (dk + F) elements against the
+                # N^2 core), then staged by the attention forward as they lie (node_attention_forward)
+                g, h = g.to(torch.bfloat16), h.to(torch.bfloat16)
         else:  # small graphs: torch's three GEMMs, no concatenation or strided slices around them
             f, g, h = self.f(V), self.g(V), self.h(V)
         if shard is not None:

@@ -225,6 +225,11 @@ SIGNATURES = {
                                              _c_i64, _c_i32, _c_i32, _c_i64, _c_i64, _c_vp, _c_size, _c_vp]),
     "grl_node_attention_bwd_rows": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
                                              _c_i64, _c_i64, _c_i32, _c_i32, _c_i64, _c_i64, _c_vp, _c_size, _c_vp]),
+    "grl_node_attention_fwd_bf16kv_path": (_c_i32, [_c_i64, _c_i64, _c_i32, _c_i32]),
+    "grl_node_attention_fwd_bf16kv_workspace_size": (_c_size, [_c_i64, _c_i64, _c_i32, _c_i32]),
+    "grl_node_attention_fwd_bf16kv_rows": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp, _c_vp,
+                                                    _c_i64, _c_i64, _c_i32, _c_i32, _c_i64, _c_i64, _c_vp, _c_size,
+                                                    _c_vp]),
     "grl_layout_graph_size": (_c_i32, [_c_vp, _c_i32, _c_vp]),
     "grl_layout_graph_dense": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_i32, _c_vp]),
     "grl_layout_graph_edges": (_c_i32, [_c_vp, _c_i32, _c_i32, _c_vp, _c_i64, _c_vp]),

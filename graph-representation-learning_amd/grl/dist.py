@@ -1744,5 +1744,10 @@ class _ShardedNodeAttention(torch.autograd.Function):
 def sharded_node_attention(Q: torch.Tensor, K: torch.Tensor, H: torch.Tensor, V: torch.Tensor, gamma: torch.Tensor,
                            sg: "ShardedGraph") -> torch.Tensor:
     """gamma * softmax_rows(Q K^T) H + V for this rank's rows of a sharded
-    graph, the softmax over all nodes (_ShardedNodeAttention)."""
+    graph, the softmax over all nodes (_ShardedNodeAttention).  float32 only:
+    the gathers and the ranged fp32 backward have no bf16 form."""
+    for t, what in ((Q, "queries"), (K, "keys"), (H, "values"), (V, "residual"), (gamma, "gamma")):
+        if t.dtype != torch.float32:
+            from ._lib import GrlError
+            raise GrlError(f"sharded_node_attention: {what} must be float32 (got {t.dtype})")
     return _ShardedNodeAttention.apply(Q, K, H, V, gamma, sg)

@@ -1248,10 +1248,18 @@ def row_linear(X: torch.Tensor, W: torch.Tensor, b=None, relu: bool = False, pat
 
 # ---------------------------------------------------------------- attention
 def _attn_check(Q, K, H, V, gamma):
+    """Shapes and dtypes.  V and gamma are float32; K and H are both float32 or
+    both bfloat16 (tables stored as bf16); Q is float32 or bfloat16."""
     for t, what in ((Q, "queries"), (K, "keys"), (H, "values"), (V, "residual"), (gamma, "gamma")):
         _require_device(t, what)
+    for t, what in ((V, "residual"), (gamma, "gamma")):
         if t.dtype != torch.float32:
             raise _lib.GrlError(f"attention {what} must be float32 (got {t.dtype})")
+    if Q.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.GrlError(f"attention queries must be float32 or bfloat16 (got {Q.dtype})")
+    if K.dtype != H.dtype or K.dtype not in (torch.float32, torch.bfloat16):
+        raise _lib.GrlError(f"attention keys and values must both be float32 or both bfloat16 (got {K.dtype}, "
+                            f"{H.dtype})")
     if Q.dim() != 3 or K.shape != Q.shape or H.dim() != 3 or H.shape[:2] != Q.shape[:2] or V.shape != H.shape \
             or gamma.shape != (H.shape[2],):
         raise _lib.GrlError(f"attention shapes: Q {tuple(Q.shape)}, K {tuple(K.shape)}, H {tuple(H.shape)}, "
@@ -1295,9 +1303,13 @@ def node_attention_forward(Q, K, H, V, gamma, stats: bool = False, q_range=None)
     stats=True also returns (o_norm, row_max, row_sum) for the backward.
     q_range=(q0, q1): only those query rows are computed (the other rows of
     the outputs are zeros) -- a node-range shard's queries against every key
-    (grl_node_attention_fwd_rows)."""
+    (grl_node_attention_fwd_rows).
+    K and H may both be bfloat16 (tables stored as bf16): where
+    grl_node_attention_fwd_bf16kv_path allows, the kernel stages them as they
+    lie (grl_node_attention_fwd_bf16kv_rows); elsewhere they are widened and
+    the fp32 call runs.  A bfloat16 Q is widened."""
     _attn_check(Q, K, H, V, gamma)
-    Q, K, H, V, gamma = (t.contiguous() for t in (Q, K, H, V, gamma))
+    Q, K, H, V, gamma = (t.contiguous() for t in (Q.float(), K, H, V, gamma))
     B, N, dk = Q.shape
     dv = H.shape[2]
     q0, q1 = (0, N) if q_range is None else (int(q_range[0]), int(q_range[1]))
@@ -1315,6 +1327,17 @@ def node_attention_forward(Q, K, H, V, gamma, stats: bool = False, q_range=None)
     onorm = alloc(V) if stats else None
     rmax = alloc(V[..., 0]) if stats else None
     rsum = (torch.ones_like(V[..., 0]) if q_range is not None else torch.empty_like(V[..., 0])) if stats else None
+    lib = _lib.lib()
+    if K.dtype == torch.bfloat16 and lib.grl_node_attention_fwd_bf16kv_path(B, N, dk, dv) \
+            and K.data_ptr() % 16 == 0 and H.data_ptr() % 16 == 0:
+        n = lib.grl_node_attention_fwd_bf16kv_workspace_size(B, N, dk, dv)  # the key split's partials only
+        ws = torch.empty(n, dtype=torch.uint8, device=V.device) if n else None
+        call("grl_node_attention_fwd_bf16kv_rows", Q.data_ptr(), K.data_ptr(), H.data_ptr(), V.data_ptr(),
+             gamma.data_ptr(), out.data_ptr(), _ptr(onorm), _ptr(rmax), _ptr(rsum), B, N, dk, dv, q0, q1, _ptr(ws), n,
+             current_stream_handle(V.device))
+        return (out, onorm, rmax, rsum) if stats else out
+    if K.dtype == torch.bfloat16:  # no bf16 form of this call: the fp32 entry on the widened tables
+        K, H = K.float(), H.float()
     ws, ws_bytes = _attn_workspace(B, N, dk, dv, V.device)
     call("grl_node_attention_fwd_rows", Q.data_ptr(), K.data_ptr(), H.data_ptr(), V.data_ptr(), gamma.data_ptr(),
          out.data_ptr(), _ptr(onorm), _ptr(rmax), _ptr(rsum), B, N, dk, dv, q0, q1, _ptr(ws), ws_bytes,
@@ -1326,7 +1349,13 @@ def node_attention_backward(Q, K, H, gamma, onorm, rmax, rsum, dout, q_range=Non
     """(dQ, dK, dH) of out = gamma * softmax(Q K^T) H + V for the output
     gradient dout, from the forward's stats (grl_node_attention_bwd).
     q_range=(q0, q1): only those queries -- dQ of the range (other rows
-    zero), dK / dH of every key from the range's queries alone (partials)."""
+    zero), dK / dH of every key from the range's queries alone (partials).
+    float32 Q, K, H and stats only (the kernels read and write fp32; a caller
+    holding bf16 tables widens them, as _NodeAttention does)."""
+    for t, what in ((Q, "queries"), (K, "keys"), (H, "values"), (gamma, "gamma"), (onorm, "o_norm"),
+                    (rmax, "row_max"), (rsum, "row_sum")):
+        if t.dtype != torch.float32:
+            raise _lib.GrlError(f"attention backward: {what} must be float32 (got {t.dtype})")
     dout = dout.contiguous().float()
     B, N, dk = Q.shape
     dv = H.shape[2]
@@ -1364,9 +1393,12 @@ class _NodeAttention(torch.autograd.Function):
     def backward(ctx, dout):
         Q, K, H, gamma, onorm, rmax, rsum = ctx.saved_tensors
         dout = dout.contiguous().float()
-        dQ, dK, dH = node_attention_backward(Q, K, H, gamma, onorm, rmax, rsum, dout)
+        # bf16 K / H (saved as they came): widened once for the fp32 backward, whose saved
+        # o_norm / row_max / row_sum are the bf16 forward's by its contract (grl.h); a
+        # gradient follows its input's dtype
+        dQ, dK, dH = node_attention_backward(Q.float(), K.float(), H.float(), gamma, onorm, rmax, rsum, dout)
         dgamma = (dout * onorm).sum((0, 1))
-        return dQ, dK, dH, dout, dgamma
+        return dQ.to(Q.dtype), dK.to(K.dtype), dH.to(H.dtype), dout, dgamma
 
 
 def node_self_attention(Q: torch.Tensor, K: torch.Tensor, H: torch.Tensor, V: torch.Tensor,

@@ -842,6 +842,48 @@ int grl_node_attention_bwd_rows(const float* Q, const float* K, const float* H,
                                 int64_t q_end, void* workspace,
                                 size_t workspace_bytes, grl_stream_t stream);
 
+/* The forward over key / value tables STORED as bf16: K16 [B, N, dk] and
+ * H16 [B, N, dv], contiguous bf16 bits.  Q, V, gamma and every output are
+ * fp32 and mean what they mean in grl_node_attention_fwd_rows; the whole
+ * range (0, N) is the unranged call.  A bf16 value is plane 0 of its three-
+ * way split with planes 1 and 2 equal to +0, so the kernel stages the
+ * caller's tables as they lie (no split pass, no plane workspace) and runs
+ * three plane products per MFMA tile where the fp32 entry runs six.
+ *   _path (host only): 1 exactly when the tables can be staged as they lie:
+ * dk in {16, 32}, dv in {32, 64, 128, 256} and the path option attn_x6 is
+ * 1; else 0.
+ *   The call: GRL_E_UNSUPPORTED where _path is 0 or K16 / H16 is not 16 B-
+ * aligned -- there is no second path inside the library; the caller widens
+ * the tables and calls grl_node_attention_fwd_rows.  Empty cases (B == 0,
+ * N == 0, q_begin == q_end: GRL_OK) and argument checks (NULLs, row_max /
+ * row_sum both or none, the range inside [0, N]: GRL_E_INVALID, decided on
+ * the host) are those of the fp32 entry.  No host sync.
+ *   `workspace` (_workspace_size bytes, or NULL) holds only the key split's
+ * partials: the split is the fp32 entry's (a function of B and N alone);
+ * NULL or too small runs unsplit.  The pipelined kernel runs at every N.
+ * attn_fwd8 = 0 selects 4-wave workgroups, as for fp32; attn_pipe is
+ * ignored (no unpipelined bf16 form exists).
+ *   Contract, for finite inputs: row_max and row_sum are BITWISE those of
+ * grl_node_attention_fwd_rows on the widened K16 and H16 under the default
+ * options (attn_x6 = 1).  out and o_norm are EQUAL AS VALUES: bitwise,
+ * except that a zero may differ in sign -- an output accumulator rescaled
+ * between key blocks can underflow to -0, which the fp32 kernel's zero-plane
+ * products turn into +0 and which stays -0 when they are skipped.  Not
+ * bitwise against the fp32-MFMA kernels (attn_x6 = 0).                    */
+int32_t grl_node_attention_fwd_bf16kv_path(int64_t B, int64_t N, int32_t dk,
+                                           int32_t dv);
+size_t grl_node_attention_fwd_bf16kv_workspace_size(int64_t B, int64_t N,
+                                                    int32_t dk, int32_t dv);
+int grl_node_attention_fwd_bf16kv_rows(const float* Q, const uint16_t* K16,
+                                       const uint16_t* H16, const float* V,
+                                       const float* gamma, float* out,
+                                       float* o_norm, float* row_max,
+                                       float* row_sum, int64_t B, int64_t N,
+                                       int32_t dk, int32_t dv, int64_t q_begin,
+                                       int64_t q_end, void* workspace,
+                                       size_t workspace_bytes,
+                                       grl_stream_t stream);
+
 /* ---------------------------------------------------------------------- */
 /* Graph formats                                                           */
 /* ---------------------------------------------------------------------- */
