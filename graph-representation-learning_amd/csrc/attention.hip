@@ -2514,16 +2514,48 @@ void with_bool(bool v, F&& f) {
     f(std::false_type{});
 }
 
+// without partials to write there is no split: one piece over the whole range
+void attn_unsplit(AttnArgs& a, int& S) {
+  if (!a.part) S = 1;
+  if (S == 1) {
+    a.part = a.part2 = nullptr;
+    a.kr = a.N;
+  }
+}
+
+// what follows a forward kernel's launch: the key split's (o, m, l) partials into out and the statistics
+int attn_fwd_combine(const AttnArgs& a, int64_t B, int S, hipStream_t st) {
+  if (S > 1) {
+    GRL_LAUNCH_CHECK();
+    const int64_t rows = B * a.N;
+    const unsigned red = (unsigned)std::min<int64_t>(ceil_div(rows * std::max(a.dv, 1), 256), 8192);
+    hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3(red), dim3(256), 0, st, a, rows, S);
+  }
+  GRL_LAUNCH_CHECK();
+  return GRL_OK;
+}
+
+// The pipelined forward's launches, for attn_fwd_x6p_kernel (planes of fp32
+// tables) and attn_fwd_x3p_kernel (bf16 tables) alike: 256 queries per 8-wave
+// workgroup unless attn_fwd8 = 0 (128 on 4 waves), then the combine.
+// launch(split, waves, grid) launches the family's instantiation.
+template <class F>
+int launch_attn_fwd_pipelined(const AttnArgs& a, int64_t B, int S, hipStream_t st, F&& launch) {
+  with_bool(attn_fwd8_enabled(), [&](auto wide) {
+    using NW = std::integral_constant<int, wide() ? 8 : 4>;
+    const dim3 grid((unsigned)ceil_div(a.q1 - a.q0, 32 * NW::value), (unsigned)B, (unsigned)S);
+    with_bool(S > 1, [&](auto s) { launch(s, NW{}, grid); });
+  });
+  return attn_fwd_combine(a, B, S, st);
+}
+
 template <int DKP, int NT>
 int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t st) {
   AttnArgs a = a0;
   // dk in (32, 64] (NodeSelfAtten of input_dim > 256): the fp32-MFMA kernels only
   const bool x6 = DKP <= 32 && attn_x6_enabled() && (pass == PASS_FWD || NT == 4);
-  if (!x6 || !a.part) S = 1;
-  if (S == 1) {
-    a.part = a.part2 = nullptr;
-    a.kr = a.N;
-  }
+  if (!x6) S = 1;
+  attn_unsplit(a, S);
   // query-stationary passes (forward, dQ) cover the queries [q0, q1); dK / dH every key
   const int64_t nq = a.q1 - a.q0;
   if (pass != PASS_BWD_KV && nq <= 0) return GRL_OK;  // no query rows: no forward / dQ work
@@ -2543,24 +2575,14 @@ int launch_attn(AttnPass pass, const AttnArgs& a0, int64_t B, int S, hipStream_t
     else
       hipLaunchKernelGGL((attn_bwd_kv_kernel<DKP, NT>), grid, dim3(256), 0, st, a);
   } else if (pass == PASS_FWD && x6) {
-    if (pre && attn_pipe_enabled() && attn_fwd8_enabled()) {  // 256 queries per workgroup
-      const dim3 g8((unsigned)ceil_div(nq, 256), (unsigned)B, (unsigned)S);
-      with_bool(S > 1, [&](auto s) {
-        hipLaunchKernelGGL((attn_fwd_x6p_kernel<DKP, NT, s(), 8>), g8, dim3(512), 0, st, a);
+    if (pre && attn_pipe_enabled())
+      return launch_attn_fwd_pipelined(a, B, S, st, [&](auto s, auto nw, dim3 g) {
+        hipLaunchKernelGGL((attn_fwd_x6p_kernel<DKP, NT, s(), nw()>), g, dim3(64 * nw()), 0, st, a);
       });
-    } else if (pre && attn_pipe_enabled()) {
-      with_bool(S > 1, [&](auto s) {
-        hipLaunchKernelGGL((attn_fwd_x6p_kernel<DKP, NT, s()>), grid, dim3(256), 0, st, a);
-      });
-    } else {
-      pre_split([&](auto p, auto s) {
-        hipLaunchKernelGGL((attn_fwd_x6_kernel<DKP, NT, p(), s()>), grid, dim3(256), 0, st, a);
-      });
-    }
-    if (S > 1) {
-      GRL_LAUNCH_CHECK();
-      hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3(red), dim3(256), 0, st, a, rows, S);
-    }
+    pre_split([&](auto p, auto s) {
+      hipLaunchKernelGGL((attn_fwd_x6_kernel<DKP, NT, p(), s()>), grid, dim3(256), 0, st, a);
+    });
+    return attn_fwd_combine(a, B, S, st);
   } else if (pass == PASS_FWD) {
     hipLaunchKernelGGL((attn_fwd_kernel<DKP, NT>), grid, dim3(256), 0, st, a);
   } else if (x6) {  // backward x6: dv in (96, 128]
@@ -2693,43 +2715,20 @@ int dispatch(AttnPass pass, const AttnArgs& a, int64_t B, int S, hipStream_t st)
 
 // The forward over bf16 K / H tables (a.Kpl, a.Hpl: the tables themselves,
 // dk == DKP and dv == 32 NT): attn_fwd_x3p_kernel at every N (no split launch
-// to amortise, so no row threshold), 8-wave workgroups unless attn_fwd8 = 0.
-template <int DKP, int NT>
-int launch_attn_bf16kv(const AttnArgs& a0, int64_t B, int S, hipStream_t st) {
-  AttnArgs a = a0;
-  if (!a.part) S = 1;
-  if (S == 1) {
-    a.part = nullptr;
-    a.kr = a.N;
-  }
-  const int64_t nq = a.q1 - a.q0, rows = B * a.N;
-  if (attn_fwd8_enabled()) {  // 256 queries per workgroup
-    const dim3 g8((unsigned)ceil_div(nq, 256), (unsigned)B, (unsigned)S);
-    with_bool(S > 1, [&](auto s) {
-      hipLaunchKernelGGL((attn_fwd_x3p_kernel<DKP, NT, s(), 8>), g8, dim3(512), 0, st, a);
-    });
-  } else {
-    const dim3 grid((unsigned)ceil_div(nq, 128), (unsigned)B, (unsigned)S);
-    with_bool(S > 1, [&](auto s) {
-      hipLaunchKernelGGL((attn_fwd_x3p_kernel<DKP, NT, s()>), grid, dim3(256), 0, st, a);
-    });
-  }
-  if (S > 1) {
-    GRL_LAUNCH_CHECK();
-    const unsigned red = (unsigned)std::min<int64_t>(ceil_div(rows * a.dv, 256), 8192);
-    hipLaunchKernelGGL(attn_fwd_combine_kernel, dim3(red), dim3(256), 0, st, a, rows, S);
-  }
-  GRL_LAUNCH_CHECK();
-  return GRL_OK;
-}
-
+// to amortise, so no row threshold), through launch_attn_fwd_pipelined.
 template <int DKP>
-int dispatch_bf16kv_nt(const AttnArgs& a, int64_t B, int S, hipStream_t st) {
+int dispatch_bf16kv(AttnArgs a, int64_t B, int S, hipStream_t st) {
+  attn_unsplit(a, S);
+  auto run = [&](auto nt) {
+    return launch_attn_fwd_pipelined(a, B, S, st, [&](auto s, auto nw, dim3 g) {
+      hipLaunchKernelGGL((attn_fwd_x3p_kernel<DKP, decltype(nt)::value, s(), nw()>), g, dim3(64 * nw()), 0, st, a);
+    });
+  };
   switch (a.dv / 32) {
-    case 1: return launch_attn_bf16kv<DKP, 1>(a, B, S, st);
-    case 2: return launch_attn_bf16kv<DKP, 2>(a, B, S, st);
-    case 4: return launch_attn_bf16kv<DKP, 4>(a, B, S, st);
-    default: return launch_attn_bf16kv<DKP, 8>(a, B, S, st);
+    case 1: return run(std::integral_constant<int, 1>{});
+    case 2: return run(std::integral_constant<int, 2>{});
+    case 4: return run(std::integral_constant<int, 4>{});
+    default: return run(std::integral_constant<int, 8>{});
   }
 }
 
@@ -2739,29 +2738,81 @@ constexpr int64_t kAttnPlaneMinRows = 4096;
 // backward) and Q, dO (backward), each section 256-B aligned
 size_t attn_plane_bytes(int64_t rows, int W) { return ((size_t)3 * rows * W * 2 + 255) / 256 * 256; }
 
-// Split `src` [rows][width] into planes at *cursor (advanced); false when
+// a caller's workspace from its first 256-B boundary on; sections are laid at cur in turn
+struct AttnWorkspace {
+  unsigned char* cur;
+  const unsigned char* end;
+  AttnWorkspace(void* workspace, size_t bytes)
+      : cur(reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255)),
+        end(static_cast<unsigned char*>(workspace) + bytes) {}
+};
+
+// Split `src` [rows][width] into planes at the cursor (advanced); false when
 // the workspace is too small (the caller then runs the in-kernel split)
-bool attn_split(const float* src, int64_t rows, int width, int W, unsigned char*& cursor, const unsigned char* end,
-                const uint16_t** out, hipStream_t st) {
+bool attn_split(const float* src, int64_t rows, int width, int W, AttnWorkspace& ws, const uint16_t** out,
+                hipStream_t st) {
   const size_t need = attn_plane_bytes(rows, W);
-  if (!src || cursor + need > end) return false;
-  uint16_t* planes = reinterpret_cast<uint16_t*>(cursor);
+  if (!src || ws.cur + need > ws.end) return false;
+  uint16_t* planes = reinterpret_cast<uint16_t*>(ws.cur);
   const int64_t n4 = rows * (W / 4);
   hipLaunchKernelGGL(attn_split_rows_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n4, 256), 8192)), dim3(256),
                      0, st, src, rows, width, W, planes);
-  cursor += need;
+  ws.cur += need;
   *out = planes;
   return true;
 }
 
-int check_dims(const char* who, int64_t B, int64_t N, int dk, int dv) {
+// the sizes and the query rows [q_begin, q_end) of a _rows entry
+int check_dims(const char* who, int64_t B, int64_t N, int dk, int dv, int64_t q_begin, int64_t q_end) {
   GRL_CHECK_ARG(B >= 0 && N >= 0, "%s: negative size", who);
   // dk = 0 is legal (input_dim < 8 gives Linear(F, 0) in the reference): all
   // scores are 0 and the attention is uniform, which the kernels compute as is.
   GRL_CHECK_ARG(dk >= 0 && dk <= 64, "%s: key width %d outside [0, 64] (NodeSelfAtten: input_dim // 8)", who, dk);
   GRL_CHECK_ARG(dv >= 1 && dv <= 256, "%s: value width %d outside [1, 256]", who, dv);
   GRL_CHECK_ARG(B * ceil_div(N, 128) < 2147483647LL && B < 65536, "%s: grid too large", who);
+  GRL_CHECK_ARG(0 <= q_begin && q_begin <= q_end && q_end <= N, "%s: query rows [%lld, %lld) outside [0, %lld)", who,
+                (long long)q_begin, (long long)q_end, (long long)N);
   return GRL_OK;
+}
+
+// the forward's arguments less the key / value tables, which each entry sets as it has them (K, H or Kpl, Hpl)
+AttnArgs attn_fwd_args(const float* Q, const float* V, const float* gamma, float* out, float* o_norm, float* row_max,
+                       float* row_sum, int64_t N, int dk, int dv, int64_t q_begin, int64_t q_end) {
+  AttnArgs a{};
+  a.Q = Q;
+  a.V = V;
+  a.gamma = gamma;
+  a.out = out;
+  a.onorm = o_norm;
+  a.rmax = row_max;
+  a.rsum = row_sum;
+  a.N = N;
+  a.dk = dk;
+  a.dv = dv;
+  a.q0 = q_begin;
+  a.q1 = q_end;
+  return a;
+}
+
+// S splits' partials of `bytes` at the cursor (a.part, a.kr = kr); without room for them, or with S = 1, no split
+int attn_place_partials(AttnArgs& a, int S, int64_t kr, size_t bytes, AttnWorkspace& ws) {
+  if (S <= 1 || ws.cur + bytes > ws.end) return 1;
+  a.part = reinterpret_cast<float*>(ws.cur);
+  a.kr = kr;
+  ws.cur += (bytes + 255) / 256 * 256;
+  return S;
+}
+
+// the forward key split's (o, m, l) partials
+size_t attn_fwd_part_bytes(int S, int64_t B, int64_t N, int dv) { return (size_t)S * B * N * (dv + 2) * 4; }
+
+// The forward's key split for small N, for both forward entries.  S depends on (B, N) alone, not on the query
+// range or on how K and H are stored, so a node-range shard's query rows (grl.dist sharded attention) are
+// bitwise the whole-range call's rows, and the bf16 entry's row_max / row_sum the fp32 entry's.
+int attn_fwd_key_split(AttnArgs& a, int64_t B, AttnWorkspace& ws) {
+  int64_t kr;
+  const int S = attn_splits(B, a.N, &kr);
+  return attn_place_partials(a, S, kr, attn_fwd_part_bytes(S, B, a.N, a.dv), ws);
 }
 
 }  // namespace
@@ -2774,7 +2825,8 @@ extern "C" size_t grl_node_attention_workspace_size(int64_t B, int64_t N, int32_
   const int64_t rows = B * N;
   int64_t kr;
   const int S = attn_splits(B, N, &kr);
-  const size_t part = S > 1 ? ((size_t)S * rows * (dv + std::max(dk, 2) + 2) * 4 + 255) / 256 * 256 : 0;
+  // one section for the forward's partials and the backward's (dv + dk wide): the forward's at dv + max(dk, 2)
+  const size_t part = S > 1 ? (attn_fwd_part_bytes(S, B, N, dv + std::max(dk, 2)) + 255) / 256 * 256 : 0;
   const size_t planes =
       rows >= kAttnPlaneMinRows ? 2 * attn_plane_bytes(rows, 32) + 2 * attn_plane_bytes(rows, attn_dvp(dv)) : 0;
   return planes + part ? planes + part + 512 : 0;
@@ -2813,53 +2865,29 @@ extern "C" int grl_node_attention_fwd_rows(const float* Q, const float* K, const
                                            int64_t q_begin, int64_t q_end, void* workspace, size_t workspace_bytes,
                                            grl_stream_t stream) {
   TraceRange trace_("grl_node_attention_fwd");
-  int rc = check_dims("grl_node_attention_fwd", B, N, dk, dv);
+  int rc = check_dims("grl_node_attention_fwd", B, N, dk, dv, q_begin, q_end);
   if (rc) return rc;
-  GRL_CHECK_ARG(0 <= q_begin && q_begin <= q_end && q_end <= N, "grl_node_attention_fwd: query rows [%lld, %lld) "
-                "outside [0, %lld)", (long long)q_begin, (long long)q_end, (long long)N);
   if (q_begin == q_end) return GRL_OK;
   if (B == 0 || N == 0) return GRL_OK;
   GRL_CHECK_ARG((dk == 0 || (Q && K)) && H && V && gamma && out, "grl_node_attention_fwd: NULL pointer");
   GRL_CHECK_ARG((row_max == nullptr) == (row_sum == nullptr), "grl_node_attention_fwd: row_max/row_sum: both or none");
-  AttnArgs a{};
-  a.Q = Q;
+  AttnArgs a = attn_fwd_args(Q, V, gamma, out, o_norm, row_max, row_sum, N, dk, dv, q_begin, q_end);
   a.K = K;
   a.H = H;
-  a.V = V;
-  a.gamma = gamma;
-  a.out = out;
-  a.onorm = o_norm;
-  a.rmax = row_max;
-  a.rsum = row_sum;
-  a.N = N;
-  a.dk = dk;
-  a.dv = dv;
-  a.q0 = q_begin;
-  a.q1 = q_end;
   hipStream_t st = as_stream(stream);
   int S = 1;
   // below ~4k rows the per-call split launches cost more than the in-kernel
   // splits they save (a 74-node page: 2 extra launches per call)
   if (workspace && attn_x6_enabled() && dk <= 32) {  // split K and H once for every query block
-    unsigned char* cur = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    const unsigned char* end = static_cast<unsigned char*>(workspace) + workspace_bytes;
+    AttnWorkspace ws(workspace, workspace_bytes);
     const uint16_t *kp = nullptr, *hp = nullptr;
-    if (B * N >= kAttnPlaneMinRows && attn_split(K, B * N, dk, attn_dkp(dk), cur, end, &kp, st) &&
-        attn_split(H, B * N, dv, attn_dvp(dv), cur, end, &hp, st)) {
+    if (B * N >= kAttnPlaneMinRows && attn_split(K, B * N, dk, attn_dkp(dk), ws, &kp, st) &&
+        attn_split(H, B * N, dv, attn_dvp(dv), ws, &hp, st)) {
       a.Kpl = kp;
       a.Hpl = hp;
     }
     GRL_LAUNCH_CHECK();
-    int64_t kr;
-    // small N: key split with (o, m, l) partials.  The split depends on N alone, not on the query range, so
-    // a node-range shard's query rows (grl.dist sharded attention) are bitwise the whole-range call's rows.
-    S = attn_splits(B, N, &kr);
-    if (S > 1 && cur + (size_t)S * B * N * (dv + 2) * 4 <= end) {
-      a.part = reinterpret_cast<float*>(cur);
-      a.kr = kr;
-    } else {
-      S = 1;
-    }
+    S = attn_fwd_key_split(a, B, ws);
   }
   return dispatch(PASS_FWD, a, B, S, st);
 }
@@ -2877,7 +2905,7 @@ extern "C" size_t grl_node_attention_fwd_bf16kv_workspace_size(int64_t B, int64_
   if (B <= 0 || N <= 0 || !grl_node_attention_fwd_bf16kv_path(B, N, dk, dv)) return 0;
   int64_t kr;
   const int S = attn_splits(B, N, &kr);  // the key split's (o, m, l) partials, nothing else
-  return S > 1 ? ((size_t)S * B * N * (dv + 2) * 4 + 255) / 256 * 256 + 512 : 0;
+  return S > 1 ? (attn_fwd_part_bytes(S, B, N, dv) + 255) / 256 * 256 + 512 : 0;
 }
 
 extern "C" int grl_node_attention_fwd_bf16kv_rows(const float* Q, const uint16_t* K16, const uint16_t* H16,
@@ -2886,10 +2914,8 @@ extern "C" int grl_node_attention_fwd_bf16kv_rows(const float* Q, const uint16_t
                                                   int32_t dv, int64_t q_begin, int64_t q_end, void* workspace,
                                                   size_t workspace_bytes, grl_stream_t stream) {
   TraceRange trace_("grl_node_attention_fwd_bf16kv");
-  int rc = check_dims("grl_node_attention_fwd_bf16kv", B, N, dk, dv);
+  int rc = check_dims("grl_node_attention_fwd_bf16kv", B, N, dk, dv, q_begin, q_end);
   if (rc) return rc;
-  GRL_CHECK_ARG(0 <= q_begin && q_begin <= q_end && q_end <= N, "grl_node_attention_fwd_bf16kv: query rows "
-                "[%lld, %lld) outside [0, %lld)", (long long)q_begin, (long long)q_end, (long long)N);
   if (q_begin == q_end) return GRL_OK;
   if (B == 0 || N == 0) return GRL_OK;
   GRL_CHECK_ARG((dk == 0 || (Q && K16)) && H16 && V && gamma && out, "grl_node_attention_fwd_bf16kv: NULL pointer");
@@ -2901,36 +2927,16 @@ extern "C" int grl_node_attention_fwd_bf16kv_rows(const float* Q, const uint16_t
   if ((reinterpret_cast<uintptr_t>(K16) | reinterpret_cast<uintptr_t>(H16)) & 15)
     GRL_FAIL(GRL_E_UNSUPPORTED, "grl_node_attention_fwd_bf16kv: K16 / H16 not 16 B-aligned: widen them and call "
              "grl_node_attention_fwd_rows");
-  AttnArgs a{};
-  a.Q = Q;
+  AttnArgs a = attn_fwd_args(Q, V, gamma, out, o_norm, row_max, row_sum, N, dk, dv, q_begin, q_end);
   a.Kpl = K16;
   a.Hpl = H16;
-  a.V = V;
-  a.gamma = gamma;
-  a.out = out;
-  a.onorm = o_norm;
-  a.rmax = row_max;
-  a.rsum = row_sum;
-  a.N = N;
-  a.dk = dk;
-  a.dv = dv;
-  a.q0 = q_begin;
-  a.q1 = q_end;
   int S = 1;
-  if (workspace) {  // the key split of grl_node_attention_fwd_rows: S depends on (B, N) alone
-    unsigned char* cur = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    const unsigned char* end = static_cast<unsigned char*>(workspace) + workspace_bytes;
-    int64_t kr;
-    S = attn_splits(B, N, &kr);
-    if (S > 1 && cur + (size_t)S * B * N * (dv + 2) * 4 <= end) {
-      a.part = reinterpret_cast<float*>(cur);
-      a.kr = kr;
-    } else {
-      S = 1;
-    }
+  if (workspace) {
+    AttnWorkspace ws(workspace, workspace_bytes);
+    S = attn_fwd_key_split(a, B, ws);
   }
   hipStream_t st = as_stream(stream);
-  return dk == 16 ? dispatch_bf16kv_nt<16>(a, B, S, st) : dispatch_bf16kv_nt<32>(a, B, S, st);
+  return dk == 16 ? dispatch_bf16kv<16>(a, B, S, st) : dispatch_bf16kv<32>(a, B, S, st);
 }
 
 extern "C" int grl_node_attention_bwd_rows(const float* Q, const float* K, const float* H, const float* dO,
@@ -2939,10 +2945,8 @@ extern "C" int grl_node_attention_bwd_rows(const float* Q, const float* K, const
                                            int64_t q_begin, int64_t q_end, void* workspace, size_t workspace_bytes,
                                            grl_stream_t stream) {
   TraceRange trace_("grl_node_attention_bwd");
-  int rc = check_dims("grl_node_attention_bwd", B, N, dk, dv);
+  int rc = check_dims("grl_node_attention_bwd", B, N, dk, dv, q_begin, q_end);
   if (rc) return rc;
-  GRL_CHECK_ARG(0 <= q_begin && q_begin <= q_end && q_end <= N, "grl_node_attention_bwd: query rows [%lld, %lld) "
-                "outside [0, %lld)", (long long)q_begin, (long long)q_end, (long long)N);
   if (B == 0 || N == 0) return GRL_OK;
   GRL_CHECK_ARG((dk == 0 || (Q && K && dQ && dK)) && H && dO && row_max && row_sum && D && dH,
                 "grl_node_attention_bwd: NULL pointer");
@@ -2966,34 +2970,27 @@ extern "C" int grl_node_attention_bwd_rows(const float* Q, const float* K, const
   hipStream_t st = as_stream(stream);
   int S = 1;
   if (workspace && attn_x6_enabled() && attn_dvp(dv) == 128 && dk <= 32) {  // the x6 backward's operands
-    unsigned char* cur = reinterpret_cast<unsigned char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    const unsigned char* end = static_cast<unsigned char*>(workspace) + workspace_bytes;
+    AttnWorkspace ws(workspace, workspace_bytes);
     const uint16_t *kp = nullptr, *hp = nullptr, *qp = nullptr, *op = nullptr;
-    if (B * N >= kAttnPlaneMinRows && attn_split(K, B * N, dk, 32, cur, end, &kp, st) &&
-        attn_split(H, B * N, dv, 128, cur, end, &hp, st) &&
-        attn_split(Q, B * N, dk, 32, cur, end, &qp, st) && attn_split(dO, B * N, dv, 128, cur, end, &op, st)) {
+    if (B * N >= kAttnPlaneMinRows && attn_split(K, B * N, dk, 32, ws, &kp, st) &&
+        attn_split(H, B * N, dv, 128, ws, &hp, st) &&
+        attn_split(Q, B * N, dk, 32, ws, &qp, st) && attn_split(dO, B * N, dv, 128, ws, &op, st)) {
       a.Kpl = kp;
       a.Hpl = hp;
       a.Qpl = qp;
       a.Opl = op;
     }
     GRL_LAUNCH_CHECK();
-    int64_t kr;
+    int64_t kr = N;
     S = ranged ? 1 : attn_splits(B, N, &kr);  // small N: key / query split with ordered partial sums
-    if (S > 1 && cur + (size_t)S * B * N * (dv + dk) * 4 <= end) {
-      a.part = reinterpret_cast<float*>(cur);
-      a.kr = kr;
-      cur += ((size_t)S * B * N * (dv + dk) * 4 + 255) / 256 * 256;
-    } else {
-      S = 1;
-    }
+    S = attn_place_partials(a, S, kr, (size_t)S * B * N * (dv + dk) * 4, ws);
     const size_t qs = ranged ? 0 : attn_qslab_bytes(B, N, dk, dv);  // ranged: the dQ kernel (no slabs)
     const uint16_t* q16 = nullptr;
-    if (qs && a.Qpl && dk > 0 && cur + qs <= end) {
-      a.qslab = reinterpret_cast<float*>(cur);
+    if (qs && a.Qpl && dk > 0 && ws.cur + qs <= ws.end) {
+      a.qslab = reinterpret_cast<float*>(ws.cur);
       a.kq_chunk = attn_qslab_chunk(B, N);
-      cur += qs;
-      if (attn_split(Q, B * N, dk, 16, cur, end, &q16, st)) {
+      ws.cur += qs;
+      if (attn_split(Q, B * N, dk, 16, ws, &q16, st)) {
         a.Qpl16 = q16;
       } else {
         a.qslab = nullptr;

@@ -1082,7 +1082,7 @@ __global__ __launch_bounds__(512) void gemm_x6t_kernel(GemmArgs p) {
 // stages' swizzle, the staging one step ahead, the zeroing of rows past the
 // split's end, the epilogue and the host's split rule are gemm_x6t_kernel's,
 // so every dW element is summed in its order: the bits are that kernel's on
-// the widened g.  Preconditions (x3t_ok): A 16 B-aligned with lda % 4 == 0,
+// the widened g.  Preconditions (dw_x6t_ok): A 16 B-aligned with lda % 4 == 0,
 // g16 8 B-aligned with ldb % 4 == 0, M, N multiples of 4.
 constexpr int X3_STAGE = 4 * X6_PLANE;  // three A planes, then B's one
 
@@ -1234,7 +1234,7 @@ __global__ __launch_bounds__(512) void gemm_x3t_kernel(GemmArgs p, const uint16_
 // rule; so the bits are that kernel's on the widened operands.  A step is 8
 // MFMAs a wave, far less than an HBM miss: the loads run GRL_X1T_NR K16 steps
 // ahead of their LDS stash in register sets of 8 VGPRs each (1, 2 and 4 were
-// measured, §4.21).  Preconditions (x1t_ok): z16 and g16 8 B-aligned, lda % 4
+// measured, §4.21).  Preconditions (dw_x6t_ok): z16 and g16 8 B-aligned, lda % 4
 // == 0, ldb % 4 == 0, M, N multiples of 4.
 #if !defined(GRL_DIAG) || !defined(GRL_X1T_NR)
 #undef GRL_X1T_NR
@@ -1832,51 +1832,135 @@ extern "C" int grl_relu_grad_bf16_scaled(const uint16_t* g, int64_t ldg, const u
                             &scale, workspace, workspace_bytes, stream);
 }
 
-extern "C" int grl_linear_bwd_weight(const float* Z, int64_t ldz, const float* g, const float* relu_out, float* dW,
-                                     float* db, int64_t M, int32_t K, int32_t C, void* workspace,
-                                     size_t workspace_bytes, grl_stream_t stream) {
-  TraceRange trace_("grl_linear_bwd_weight");
-  GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0 && ldz >= K, "grl_linear_bwd_weight: bad sizes");
+namespace grl {
+namespace {
+// The operands of a dW entry as they are stored: Z (M x K, row stride ldz) and
+// g (M x C, row stride ldg), each fp32 or bf16, and the fp32 entry's optional
+// ReLU mask (indexed as a dense fp32 g)
+struct DwOperands {
+  const void* Z;
+  bool z16;
+  int64_t ldz;
+  const void* g;
+  bool g16;
+  int64_t ldg;
+  const float* relu_out;
+  const float* z32() const { return z16 ? nullptr : static_cast<const float*>(Z); }
+  const float* g32() const { return g16 ? nullptr : static_cast<const float*>(g); }
+  const uint16_t* zb() const { return static_cast<const uint16_t*>(Z); }
+  const uint16_t* gb() const { return static_cast<const uint16_t*>(g); }
+};
+
+// an operand's rows on the loads of its kernel: fp32 as gemm_x6t_kernel loads
+// it (16 B), bf16 on the 8 B loads of four values
+bool dw_rows_aligned(const void* p, bool is16, int64_t ld) {
+  return reinterpret_cast<uintptr_t>(p) % (is16 ? 8 : 16) == 0 && ld % 4 == 0;
+}
+
+// Whether the x6t family runs the call (gemm_x6t_kernel for fp32 operands,
+// gemm_x3t_kernel for a bf16 g, gemm_x1t_kernel for a bf16 Z and g): the
+// entry's path option (dw_bf16z / dw_bf16g; gemm_x6 is in the shape rule),
+// gemm_x6t_kernel's shape rule, each operand's alignment, and no mask
+bool dw_x6t_ok(const DwOperands& o, int64_t M, int64_t K, int64_t C) {
+  const bool option = o.z16 ? opt(OPT_DW_BF16Z) != 0 : !o.g16 || opt(OPT_DW_BF16G) != 0;
+  return option && !o.relu_out && x6t_shape_ok(M, K, C) && dw_rows_aligned(o.Z, o.z16, o.ldz) &&
+         dw_rows_aligned(o.g, o.g16, o.ldg);
+}
+
+// The x6t family's launch plan, one for its three kernels: the same splits,
+// tile order and slab reduce, which is what makes dW of the bf16 entries the
+// fp32 entry's on widened operands, bit for bit.  a is the transposed problem
+// (a.M = K rows of dW, a.N = C, a.K = M nodes); returns the slabs used.
+int x6t_plan(GemmArgs& a, float* slab, float* dW) {
+  const int splits = x6t_splits(a.K, a.M, a.N);
+  a.C = splits > 1 ? slab : dW;
+  a.k_per_split = ceil_div(ceil_div(a.K, splits), X6_K) * X6_K;
+  const int used = (int)ceil_div(a.K, a.k_per_split);
+  a.mt = ceil_div(a.M, LB_M);
+  a.nt = ceil_div(a.N, LB_N);
+  a.zt = used;
+  a.inner_n = 0;
+  return used;
+}
+
+// db = column sums of g (masked for the fp32 entry) through partials at part
+int dw_colsum(const DwOperands& o, int64_t M, int32_t C, float* part, float* db, hipStream_t st) {
+  const int zs = colsum_splits(M);
+  const int64_t rows_per = ceil_div(std::max<int64_t>(M, 1), zs);
+  const dim3 grid((unsigned)ceil_div(C, 256), (unsigned)zs);
+  if (o.g16)
+    hipLaunchKernelGGL(colsum_partial_bf16_kernel, grid, dim3(256), 0, st, o.gb(), o.ldg, M, (int64_t)C, rows_per,
+                       part);
+  else
+    hipLaunchKernelGGL(colsum_partial_kernel, grid, dim3(256), 0, st, o.g32(), o.relu_out, M, C, rows_per, part);
+  GRL_LAUNCH_CHECK();
+  hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs, db);
+  GRL_LAUNCH_CHECK();
+  return GRL_OK;
+}
+
+// grl_linear_bwd_weight, _bf16g and _bf16zg: one host path.  Outside the x6t
+// family the fp32 entry falls back to the fp32-MFMA kernel; the bf16 entries
+// have no other kernel and answer GRL_E_UNSUPPORTED.
+int linear_bwd_weight_run(const char* who, const DwOperands& o, float* dW, float* db, int64_t M, int32_t K, int32_t C,
+                          void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0, "%s: negative size", who);
+  GRL_CHECK_ARG(o.ldz >= K && o.ldg >= C, "%s: need ldz >= K and ldg >= C (ldz=%lld K=%d ldg=%lld C=%d)", who,
+                (long long)o.ldz, K, (long long)o.ldg, C);
+  GRL_CHECK_ARG((!o.z16 || reinterpret_cast<uintptr_t>(o.Z) % 2 == 0) &&
+                    (!o.g16 || reinterpret_cast<uintptr_t>(o.g) % 2 == 0),
+                "%s: a bf16 Z or g must be 2-B aligned", who);
   if (K == 0 || C == 0) return GRL_OK;
+  hipStream_t st = as_stream(stream);
   if (M == 0) {  // no rows (an empty node-range shard): dW = 0, db = 0
-    GRL_CHECK_ARG(dW, "grl_linear_bwd_weight: NULL pointer");
-    hipStream_t st = as_stream(stream);
+    GRL_CHECK_ARG(dW, "%s: NULL pointer", who);
     if (hipMemsetAsync(dW, 0, (size_t)K * C * sizeof(float), st) != hipSuccess ||
         (db && hipMemsetAsync(db, 0, (size_t)C * sizeof(float), st) != hipSuccess))
-      GRL_FAIL(GRL_E_HIP, "grl_linear_bwd_weight: hipMemsetAsync failed");
+      GRL_FAIL(GRL_E_HIP, "%s: hipMemsetAsync failed", who);
     return GRL_OK;
   }
-  GRL_CHECK_ARG(Z && g && dW, "grl_linear_bwd_weight: NULL pointer");
+  GRL_CHECK_ARG(o.Z && o.g && dW, "%s: NULL pointer", who);
+  const bool x6t = dw_x6t_ok(o, M, K, C);
+  if (!x6t && o.g16)
+    GRL_FAIL(GRL_E_UNSUPPORTED, "%s: outside the bf16 dW path (M %lld, K %d, C %d, the operands' alignment or the "
+             "%s / gemm_x6 options; see %s_workspace_query)", who, (long long)M, K, C,
+             o.z16 ? "dw_bf16z" : "dw_bf16g", who);
   const size_t need = grl_linear_bwd_weight_workspace_size(M, K, C);
   if (!workspace || workspace_bytes < need)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_linear_bwd_weight: workspace %zu < %zu", workspace_bytes, need);
-  hipStream_t st = as_stream(stream);
+    GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
   float* slab = static_cast<float*>(workspace);
-  // A(m=kk, k=row) = Z[row][kk]: rows of Z are M-contiguous for fixed k; B(k=row, n=c) = g[row][c]; C set below
-  GemmArgs a = gemm_args(Z, ldz, g, C, nullptr, C, K, C, M);
-  a.Bmask = relu_out;
-  const bool aligned = al16(Z) && al16(g) && (!relu_out || al16(relu_out)) && ldz % 4 == 0 && C % 4 == 0 && K % 4 == 0;
+  // A(m=kk, k=row) = Z[row][kk]: rows of Z are M-contiguous for fixed k; B(k=row, n=c) = g[row][c]; C set below.
+  // A bf16 operand goes to its kernel as an argument of its own and leaves a NULL here.
+  GemmArgs a = gemm_args(o.z32(), o.ldz, o.g32(), o.ldg, nullptr, C, K, C, M);
+  a.Bmask = o.relu_out;
   int used;
-  if (aligned && !relu_out && x6t_shape_ok(M, K, C)) {  // large M: fp32 on the bf16 matrix cores
+  if (x6t) {  // large M: fp32 on the bf16 matrix cores
     // (a v_mfma_f32_16x16x32_bf16 form -- 128 x 256 tiles, 32-deep stages, conflict-free transposed reads,
     // with or without the next stage's split interleaved -- was 10 % slower at C3: 5.31 / 5.38 vs 4.81 ms,
     // profiles/r05_ab_dw16.txt; 16 x 16 fragments cost a third more LDS reads per flop here)
-    const int splits = x6t_splits(M, K, C);
-    a.C = splits > 1 ? slab : dW;
-    a.k_per_split = ceil_div(ceil_div(M, splits), X6_K) * X6_K;
-    used = (int)ceil_div(M, a.k_per_split);
-    a.mt = ceil_div(a.M, LB_M);
-    a.nt = ceil_div(a.N, LB_N);
-    a.zt = used;
-    a.inner_n = 0;
+    used = x6t_plan(a, slab, dW);
     GRL_CHECK_ARG(a.mt * a.nt * a.zt < 2147483647LL, "gemm: grid too large");
-    const dim3 grid((unsigned)(a.mt * a.nt * a.zt));
-    if (used > 1)
-      hipLaunchKernelGGL(gemm_x6t_kernel<EPI_SLAB>, grid, dim3(512), 0, st, a);
-    else
-      hipLaunchKernelGGL(gemm_x6t_kernel<EPI_STORE>, grid, dim3(512), 0, st, a);
+    const dim3 grid((unsigned)(a.mt * a.nt * a.zt)), block(512);
+    if (o.z16) {
+      if (used > 1)
+        hipLaunchKernelGGL(gemm_x1t_kernel<EPI_SLAB>, grid, block, 0, st, a, o.zb(), o.gb());
+      else
+        hipLaunchKernelGGL(gemm_x1t_kernel<EPI_STORE>, grid, block, 0, st, a, o.zb(), o.gb());
+    } else if (o.g16) {
+      if (used > 1)
+        hipLaunchKernelGGL(gemm_x3t_kernel<EPI_SLAB>, grid, block, 0, st, a, o.gb());
+      else
+        hipLaunchKernelGGL(gemm_x3t_kernel<EPI_STORE>, grid, block, 0, st, a, o.gb());
+    } else {
+      if (used > 1)
+        hipLaunchKernelGGL(gemm_x6t_kernel<EPI_SLAB>, grid, block, 0, st, a);
+      else
+        hipLaunchKernelGGL(gemm_x6t_kernel<EPI_STORE>, grid, block, 0, st, a);
+    }
     GRL_LAUNCH_CHECK();
   } else {
+    const bool aligned = dw_rows_aligned(o.Z, false, o.ldz) && dw_rows_aligned(o.g, false, o.ldg) &&
+                         (!o.relu_out || al16(o.relu_out)) && K % 4 == 0;
     const int splits = pick_splits(K, C, M);
     a.C = splits > 1 ? slab : dW;
     a.k_per_split = ceil_div(ceil_div(M, splits), GEMM_BK) * GEMM_BK;
@@ -1891,183 +1975,47 @@ extern "C" int grl_linear_bwd_weight(const float* Z, int64_t ldz, const float* g
                        st, slab, n, used, dW);
     GRL_LAUNCH_CHECK();
   }
-  if (db) {
-    const int zs = colsum_splits(M);
-    float* part = slab + (size_t)wgt_slab_splits(M, K, C) * K * C;
-    const int64_t rows_per = ceil_div(std::max<int64_t>(M, 1), zs);
-    hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)ceil_div(C, 256), (unsigned)zs), dim3(256), 0, st, g,
-                       relu_out, M, C, rows_per, part);
-    GRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs,
-                       db);
-    GRL_LAUNCH_CHECK();
-  }
-  return GRL_OK;
+  return db ? dw_colsum(o, M, C, slab + (size_t)wgt_slab_splits(M, K, C) * K * C, db, st) : GRL_OK;
 }
 
-namespace grl {
-namespace {
-// x3t (dW from a g stored as bf16) selection: gemm_x6t_kernel's shape rule, Z
-// as that kernel loads it (16 B), g's rows on the 8 B loads of four bf16, and
-// the dw_bf16g path option
-bool x3t_ok(const float* Z, int64_t ldz, const uint16_t* g, int64_t ldg, int64_t M, int64_t K, int64_t C) {
-  return opt(OPT_DW_BF16G) != 0 && x6t_shape_ok(M, K, C) && al16(Z) && ldz % 4 == 0 &&
-         reinterpret_cast<uintptr_t>(g) % 8 == 0 && ldg % 4 == 0;
+size_t dw_bf16_workspace_query(const DwOperands& o, int64_t M, int32_t K, int32_t C) {
+  if (!o.Z || !o.g || M <= 0 || K <= 0 || C <= 0 || o.ldz < K || o.ldg < C) return 0;
+  return dw_x6t_ok(o, M, K, C) ? grl_linear_bwd_weight_workspace_size(M, K, C) : 0;
 }
 }  // namespace
 }  // namespace grl
 
+extern "C" int grl_linear_bwd_weight(const float* Z, int64_t ldz, const float* g, const float* relu_out, float* dW,
+                                     float* db, int64_t M, int32_t K, int32_t C, void* workspace,
+                                     size_t workspace_bytes, grl_stream_t stream) {
+  grl::TraceRange trace_("grl_linear_bwd_weight");
+  return grl::linear_bwd_weight_run("grl_linear_bwd_weight", {Z, false, ldz, g, false, C, relu_out}, dW, db, M, K, C,
+                                    workspace, workspace_bytes, stream);
+}
+
 extern "C" size_t grl_linear_bwd_weight_bf16g_workspace_query(const float* Z, int64_t ldz, const uint16_t* g,
                                                               int64_t ldg, int64_t M, int32_t K, int32_t C) {
-  if (!Z || !g || M <= 0 || K <= 0 || C <= 0 || ldz < K || ldg < C) return 0;
-  return grl::x3t_ok(Z, ldz, g, ldg, M, K, C) ? grl_linear_bwd_weight_workspace_size(M, K, C) : 0;
+  return grl::dw_bf16_workspace_query({Z, false, ldz, g, true, ldg, nullptr}, M, K, C);
 }
 
 extern "C" int grl_linear_bwd_weight_bf16g(const float* Z, int64_t ldz, const uint16_t* g, int64_t ldg, float* dW,
                                            float* db, int64_t M, int32_t K, int32_t C, void* workspace,
                                            size_t workspace_bytes, grl_stream_t stream) {
-  TraceRange trace_("grl_linear_bwd_weight_bf16g");
-  GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0, "grl_linear_bwd_weight_bf16g: negative size");
-  GRL_CHECK_ARG(ldz >= K && ldg >= C,
-                "grl_linear_bwd_weight_bf16g: need ldz >= K and ldg >= C (ldz=%lld K=%d ldg=%lld C=%d)", (long long)ldz,
-                K, (long long)ldg, C);
-  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(g) % 2 == 0, "grl_linear_bwd_weight_bf16g: g must be 2-B aligned");
-  if (K == 0 || C == 0) return GRL_OK;
-  if (M == 0) {  // no rows (an empty node-range shard): dW = 0, db = 0
-    GRL_CHECK_ARG(dW, "grl_linear_bwd_weight_bf16g: NULL pointer");
-    hipStream_t st = as_stream(stream);
-    if (hipMemsetAsync(dW, 0, (size_t)K * C * sizeof(float), st) != hipSuccess ||
-        (db && hipMemsetAsync(db, 0, (size_t)C * sizeof(float), st) != hipSuccess))
-      GRL_FAIL(GRL_E_HIP, "grl_linear_bwd_weight_bf16g: hipMemsetAsync failed");
-    return GRL_OK;
-  }
-  GRL_CHECK_ARG(Z && g && dW, "grl_linear_bwd_weight_bf16g: NULL pointer");
-  if (!x3t_ok(Z, ldz, g, ldg, M, K, C))
-    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_linear_bwd_weight_bf16g: outside the bf16-gradient dW path (M %lld, K %d, C %d, "
-             "the operands' alignment or the dw_bf16g / gemm_x6 options; see "
-             "grl_linear_bwd_weight_bf16g_workspace_query)", (long long)M, K, C);
-  const size_t need = grl_linear_bwd_weight_workspace_size(M, K, C);
-  if (!workspace || workspace_bytes < need)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_linear_bwd_weight_bf16g: workspace %zu < %zu", workspace_bytes, need);
-  hipStream_t st = as_stream(stream);
-  float* slab = static_cast<float*>(workspace);
-  // gemm_x6t_kernel's launch (grl_linear_bwd_weight): the same splits, tile order and slab reduce
-  GemmArgs a = gemm_args(Z, ldz, nullptr, ldg, nullptr, C, K, C, M);
-  const int splits = x6t_splits(M, K, C);
-  a.C = splits > 1 ? slab : dW;
-  a.k_per_split = ceil_div(ceil_div(M, splits), X6_K) * X6_K;
-  const int used = (int)ceil_div(M, a.k_per_split);
-  a.mt = ceil_div(a.M, LB_M);
-  a.nt = ceil_div(a.N, LB_N);
-  a.zt = used;
-  a.inner_n = 0;
-  GRL_CHECK_ARG(a.mt * a.nt * a.zt < 2147483647LL, "gemm: grid too large");
-  const dim3 grid((unsigned)(a.mt * a.nt * a.zt));
-  if (used > 1)
-    hipLaunchKernelGGL(gemm_x3t_kernel<EPI_SLAB>, grid, dim3(512), 0, st, a, g);
-  else
-    hipLaunchKernelGGL(gemm_x3t_kernel<EPI_STORE>, grid, dim3(512), 0, st, a, g);
-  GRL_LAUNCH_CHECK();
-  if (used > 1) {
-    const int64_t n = (int64_t)K * C;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 65536)), dim3(256), 0,
-                       st, slab, n, used, dW);
-    GRL_LAUNCH_CHECK();
-  }
-  if (db) {
-    const int zs = colsum_splits(M);
-    float* part = slab + (size_t)wgt_slab_splits(M, K, C) * K * C;
-    const int64_t rows_per = ceil_div(std::max<int64_t>(M, 1), zs);
-    hipLaunchKernelGGL(colsum_partial_bf16_kernel, dim3((unsigned)ceil_div(C, 256), (unsigned)zs), dim3(256), 0, st, g,
-                       ldg, M, (int64_t)C, rows_per, part);
-    GRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs,
-                       db);
-    GRL_LAUNCH_CHECK();
-  }
-  return GRL_OK;
+  grl::TraceRange trace_("grl_linear_bwd_weight_bf16g");
+  return grl::linear_bwd_weight_run("grl_linear_bwd_weight_bf16g", {Z, false, ldz, g, true, ldg, nullptr}, dW, db, M,
+                                    K, C, workspace, workspace_bytes, stream);
 }
-
-namespace grl {
-namespace {
-// x1t (dW from a Z and a g both stored as bf16) selection: gemm_x6t_kernel's
-// shape rule, each operand's rows on the 8 B loads of four bf16, and the
-// dw_bf16z path option
-bool x1t_ok(const uint16_t* Z, int64_t ldz, const uint16_t* g, int64_t ldg, int64_t M, int64_t K, int64_t C) {
-  return opt(OPT_DW_BF16Z) != 0 && x6t_shape_ok(M, K, C) && reinterpret_cast<uintptr_t>(Z) % 8 == 0 &&
-         ldz % 4 == 0 && reinterpret_cast<uintptr_t>(g) % 8 == 0 && ldg % 4 == 0;
-}
-}  // namespace
-}  // namespace grl
 
 extern "C" size_t grl_linear_bwd_weight_bf16zg_workspace_query(const uint16_t* Z, int64_t ldz, const uint16_t* g,
                                                                int64_t ldg, int64_t M, int32_t K, int32_t C) {
-  if (!Z || !g || M <= 0 || K <= 0 || C <= 0 || ldz < K || ldg < C) return 0;
-  return grl::x1t_ok(Z, ldz, g, ldg, M, K, C) ? grl_linear_bwd_weight_workspace_size(M, K, C) : 0;
+  return grl::dw_bf16_workspace_query({Z, true, ldz, g, true, ldg, nullptr}, M, K, C);
 }
 
 extern "C" int grl_linear_bwd_weight_bf16zg(const uint16_t* Z, int64_t ldz, const uint16_t* g, int64_t ldg, float* dW,
                                             float* db, int64_t M, int32_t K, int32_t C, void* workspace,
                                             size_t workspace_bytes, grl_stream_t stream) {
-  TraceRange trace_("grl_linear_bwd_weight_bf16zg");
-  GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0, "grl_linear_bwd_weight_bf16zg: negative size");
-  GRL_CHECK_ARG(ldz >= K && ldg >= C,
-                "grl_linear_bwd_weight_bf16zg: need ldz >= K and ldg >= C (ldz=%lld K=%d ldg=%lld C=%d)",
-                (long long)ldz, K, (long long)ldg, C);
-  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(Z) % 2 == 0 && reinterpret_cast<uintptr_t>(g) % 2 == 0,
-                "grl_linear_bwd_weight_bf16zg: Z and g must be 2-B aligned");
-  if (K == 0 || C == 0) return GRL_OK;
-  if (M == 0) {  // no rows (an empty node-range shard): dW = 0, db = 0
-    GRL_CHECK_ARG(dW, "grl_linear_bwd_weight_bf16zg: NULL pointer");
-    hipStream_t st = as_stream(stream);
-    if (hipMemsetAsync(dW, 0, (size_t)K * C * sizeof(float), st) != hipSuccess ||
-        (db && hipMemsetAsync(db, 0, (size_t)C * sizeof(float), st) != hipSuccess))
-      GRL_FAIL(GRL_E_HIP, "grl_linear_bwd_weight_bf16zg: hipMemsetAsync failed");
-    return GRL_OK;
-  }
-  GRL_CHECK_ARG(Z && g && dW, "grl_linear_bwd_weight_bf16zg: NULL pointer");
-  if (!x1t_ok(Z, ldz, g, ldg, M, K, C))
-    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_linear_bwd_weight_bf16zg: outside the bf16-Z dW path (M %lld, K %d, C %d, "
-             "the operands' alignment or the dw_bf16z / gemm_x6 options; see "
-             "grl_linear_bwd_weight_bf16zg_workspace_query)", (long long)M, K, C);
-  const size_t need = grl_linear_bwd_weight_workspace_size(M, K, C);
-  if (!workspace || workspace_bytes < need)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_linear_bwd_weight_bf16zg: workspace %zu < %zu", workspace_bytes, need);
-  hipStream_t st = as_stream(stream);
-  float* slab = static_cast<float*>(workspace);
-  // gemm_x6t_kernel's launch (grl_linear_bwd_weight): the same splits, tile order and slab reduce
-  GemmArgs a = gemm_args(nullptr, ldz, nullptr, ldg, nullptr, C, K, C, M);
-  const int splits = x6t_splits(M, K, C);
-  a.C = splits > 1 ? slab : dW;
-  a.k_per_split = ceil_div(ceil_div(M, splits), X6_K) * X6_K;
-  const int used = (int)ceil_div(M, a.k_per_split);
-  a.mt = ceil_div(a.M, LB_M);
-  a.nt = ceil_div(a.N, LB_N);
-  a.zt = used;
-  a.inner_n = 0;
-  GRL_CHECK_ARG(a.mt * a.nt * a.zt < 2147483647LL, "gemm: grid too large");
-  const dim3 grid((unsigned)(a.mt * a.nt * a.zt));
-  if (used > 1)
-    hipLaunchKernelGGL(gemm_x1t_kernel<EPI_SLAB>, grid, dim3(512), 0, st, a, Z, g);
-  else
-    hipLaunchKernelGGL(gemm_x1t_kernel<EPI_STORE>, grid, dim3(512), 0, st, a, Z, g);
-  GRL_LAUNCH_CHECK();
-  if (used > 1) {
-    const int64_t n = (int64_t)K * C;
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)std::min<int64_t>(ceil_div(n, 256), 65536)), dim3(256), 0,
-                       st, slab, n, used, dW);
-    GRL_LAUNCH_CHECK();
-  }
-  if (db) {
-    const int zs = colsum_splits(M);
-    float* part = slab + (size_t)wgt_slab_splits(M, K, C) * K * C;
-    const int64_t rows_per = ceil_div(std::max<int64_t>(M, 1), zs);
-    hipLaunchKernelGGL(colsum_partial_bf16_kernel, dim3((unsigned)ceil_div(C, 256), (unsigned)zs), dim3(256), 0, st, g,
-                       ldg, M, (int64_t)C, rows_per, part);
-    GRL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)ceil_div(C, 256)), dim3(256), 0, st, part, (int64_t)C, zs,
-                       db);
-    GRL_LAUNCH_CHECK();
-  }
-  return GRL_OK;
+  grl::TraceRange trace_("grl_linear_bwd_weight_bf16zg");
+  return grl::linear_bwd_weight_run("grl_linear_bwd_weight_bf16zg", {Z, true, ldz, g, true, ldg, nullptr}, dW, db, M,
+                                    K, C, workspace, workspace_bytes, stream);
 }
+

@@ -361,6 +361,22 @@ def linear_bwd_weight(Z2: torch.Tensor, g: torch.Tensor, relu_out, want_db: bool
     return dW, db
 
 
+def _linear_bwd_weight_bf16_run(entry: str, Z: torch.Tensor, g16: torch.Tensor, want_db: bool):
+    """The checked operands through a bf16 dW entry: its workspace query (0: None,
+    before anything is allocated), dW, db and the workspace, the call."""
+    M, K = Z.shape
+    C = g16.shape[1]
+    ws_bytes = getattr(_lib.lib(), entry + "_workspace_query")(Z.data_ptr(), _ld(Z), g16.data_ptr(), _ld(g16), M, K, C)
+    if ws_bytes == 0:
+        return None
+    dW = torch.empty(K, C, dtype=torch.float32, device=g16.device)
+    db = torch.empty(C, dtype=torch.float32, device=g16.device) if want_db else None
+    ws = _workspace(ws_bytes, g16.device)
+    call(entry, Z.data_ptr(), _ld(Z), g16.data_ptr(), _ld(g16), dW.data_ptr(), _ptr(db), M, K, C, _ptr(ws), ws_bytes,
+         current_stream_handle(g16.device))
+    return dW, db
+
+
 def linear_bwd_weight_bf16(Z2: torch.Tensor, g16: torch.Tensor, want_db: bool):
     """(dW, db) = (Z2^T g16, column sums of g16) with the bfloat16 gradient read
     as stored (grl_linear_bwd_weight_bf16g: half the plane products of the
@@ -381,18 +397,7 @@ def linear_bwd_weight_bf16(Z2: torch.Tensor, g16: torch.Tensor, want_db: bool):
             or (Z2.shape[1] > 0 and Z2.stride(1) != 1) or not _rows_apart(Z2)):
         raise _lib.GrlError(f"linear_bwd_weight_bf16: Z must be a float32 [{g16.shape[0]}, K] tensor on {g16.device} "
                             "with unit column stride")
-    M, K = Z2.shape
-    C = g16.shape[1]
-    ws_bytes = _lib.lib().grl_linear_bwd_weight_bf16g_workspace_query(Z2.data_ptr(), _ld(Z2), g16.data_ptr(), _ld(g16),
-                                                                      M, K, C)
-    if ws_bytes == 0:
-        return None
-    dW = torch.empty(K, C, dtype=torch.float32, device=g16.device)
-    db = torch.empty(C, dtype=torch.float32, device=g16.device) if want_db else None
-    ws = _workspace(ws_bytes, g16.device)
-    call("grl_linear_bwd_weight_bf16g", Z2.data_ptr(), _ld(Z2), g16.data_ptr(), _ld(g16), dW.data_ptr(), _ptr(db), M, K,
-         C, _ptr(ws), ws_bytes, current_stream_handle(g16.device))
-    return dW, db
+    return _linear_bwd_weight_bf16_run("grl_linear_bwd_weight_bf16g", Z2, g16, want_db)
 
 
 def linear_bwd_weight_bf16z(Z16: torch.Tensor, g16: torch.Tensor, want_db: bool):
@@ -415,18 +420,7 @@ def linear_bwd_weight_bf16z(Z16: torch.Tensor, g16: torch.Tensor, want_db: bool)
                                 ".contiguous() first)")
     if Z16.shape[0] != g16.shape[0]:
         raise _lib.GrlError(f"linear_bwd_weight_bf16z: Z has {Z16.shape[0]} rows, g {g16.shape[0]}")
-    M, K = Z16.shape
-    C = g16.shape[1]
-    ws_bytes = _lib.lib().grl_linear_bwd_weight_bf16zg_workspace_query(Z16.data_ptr(), _ld(Z16), g16.data_ptr(),
-                                                                       _ld(g16), M, K, C)
-    if ws_bytes == 0:
-        return None
-    dW = torch.empty(K, C, dtype=torch.float32, device=g16.device)
-    db = torch.empty(C, dtype=torch.float32, device=g16.device) if want_db else None
-    ws = _workspace(ws_bytes, g16.device)
-    call("grl_linear_bwd_weight_bf16zg", Z16.data_ptr(), _ld(Z16), g16.data_ptr(), _ld(g16), dW.data_ptr(), _ptr(db), M,
-         K, C, _ptr(ws), ws_bytes, current_stream_handle(g16.device))
-    return dW, db
+    return _linear_bwd_weight_bf16_run("grl_linear_bwd_weight_bf16zg", Z16, g16, want_db)
 
 
 class _GraphLinear(torch.autograd.Function):
