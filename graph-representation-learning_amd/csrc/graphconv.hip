@@ -663,12 +663,21 @@ static int ws_spin_limit() {
 // word, which grl_check() reads and clears at the caller's next sync point.
 // ws_status_sync = 1 (debug aid) makes an eager call wait for its kernel and
 // return GRL_E_TIMEOUT itself, as round 3's entry points did.
-__device__ int g_grl_sticky;  // WS_WHO_* bits of the calls whose outputs were poisoned
+__device__ int g_grl_sticky;  // bit i: a call of WS_WHO_NAMES[i] had its outputs poisoned
 
-constexpr int WS_WHO_FWD = 1, WS_WHO_FWD_TRAIN = 2, WS_WHO_BWD_DATA = 4, WS_WHO_FWD_BF16 = 8,
-              WS_WHO_FWD_TRAIN_BF16 = 16, WS_WHO_FWD_BF16_TO_BF16 = 32, WS_WHO_FWD_TRAIN_BF16_TO_BF16 = 64,
-              WS_WHO_BWD_DATA_BF16 = 128, WS_WHO_FWD_TRAIN_BF16_Z16 = 256;
-constexpr int WS_WHO_COUNT = 9;
+// The entries that run the persistent kernel, by their bit's position in the
+// sticky word (grl_check's callers read the bits: positions never change).
+constexpr const char* WS_WHO_NAMES[] = {
+    "grl_graphconv_fwd",              "grl_graphconv_fwd_train",              "grl_graphconv_bwd_data",
+    "grl_graphconv_fwd_bf16",         "grl_graphconv_fwd_train_bf16",         "grl_graphconv_fwd_bf16_to_bf16",
+    "grl_graphconv_fwd_train_bf16_to_bf16", "grl_graphconv_bwd_data_bf16",    "grl_graphconv_fwd_train_bf16_z16"};
+constexpr int WS_WHO_COUNT = sizeof(WS_WHO_NAMES) / sizeof(WS_WHO_NAMES[0]);
+constexpr int WS_WHO_BWD_DATA = 1 << 2, WS_WHO_BWD_DATA_BF16 = 1 << 7;
+// a forward entry's bit: by its table (bf16), its out (out16), its Z (z16) and whether it writes Z at all
+constexpr int ws_who_fwd(bool bf16, bool out16, bool z16, bool train) {
+  return 1 << (z16 ? 8 : out16 ? 5 + train : bf16 ? 3 + train : train);
+}
+static const char* who_name(int who) { return WS_WHO_NAMES[__builtin_ctz(who)]; }
 
 __global__ void ws_poison_kernel(const int* __restrict__ status, float* __restrict__ a, int64_t na,
                                  float* __restrict__ b, int64_t nb, int who) {
@@ -693,18 +702,6 @@ __global__ void ws_poison_bf16_kernel(const int* __restrict__ status, uint16_t* 
     else
       b[i - na] = nan;
   }
-}
-
-static const char* who_name(int who) {
-  return who == WS_WHO_FWD                 ? "grl_graphconv_fwd"
-         : who == WS_WHO_FWD_TRAIN         ? "grl_graphconv_fwd_train"
-         : who == WS_WHO_BWD_DATA          ? "grl_graphconv_bwd_data"
-         : who == WS_WHO_FWD_BF16          ? "grl_graphconv_fwd_bf16"
-         : who == WS_WHO_FWD_TRAIN_BF16    ? "grl_graphconv_fwd_train_bf16"
-         : who == WS_WHO_FWD_BF16_TO_BF16  ? "grl_graphconv_fwd_bf16_to_bf16"
-         : who == WS_WHO_BWD_DATA_BF16     ? "grl_graphconv_bwd_data_bf16"
-         : who == WS_WHO_FWD_TRAIN_BF16_Z16 ? "grl_graphconv_fwd_train_bf16_z16"
-                                           : "grl_graphconv_fwd_train_bf16_to_bf16";
 }
 
 // a: the call's out, float [M, C] contiguous or uint16_t (bf16 bits) [M, C] with row stride ldo; b: its Z / G_agg
@@ -816,13 +813,13 @@ static void launch_ws(int F, int C, bool v, dim3 grid, hipStream_t st, int64_t M
 // persistent kernel (there is no bf16 phase-alternating kernel).  OT =
 // uint16_t (a bf16 table only): out holds bf16 bits, ldo apart a row.  ZT =
 // uint16_t (a bf16 out only): Z holds bf16 bits (grl_graphconv_fwd_train_bf16_z16).
-template <typename XT, typename OT, typename ZT = float>
-static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, const float* W,
+// who: the calling entry's sticky bit (ws_who_fwd).
+template <typename XT, typename OT, typename ZT>
+static int graphconv_fused_fwd(int who, const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, const float* W,
                                const float* bias, int C, int relu, OT* out, int64_t ldo, const GrlDropEdge* de,
-                               void* ws, hipStream_t st, ZT* Z = nullptr) {
+                               void* ws, hipStream_t st, ZT* Z) {
   constexpr bool BF16 = std::is_same<XT, uint16_t>::value;
   constexpr bool OUT16 = std::is_same<OT, uint16_t>::value;
-  constexpr bool Z16 = std::is_same<ZT, uint16_t>::value;
   static_assert(!OUT16 || BF16, "bf16 output: a bf16 table only");
   const int hs = g->has_self ? 1 : 0;
   const int64_t K = (int64_t)segments(g) * F;
@@ -834,7 +831,7 @@ static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, i
   GRL_LAUNCH_CHECK();
   const int64_t M = g->num_rows;
   const int64_t tiles = ceil_div(M, FG_R);
-  GRL_CHECK_ARG(tiles < 2147483647LL, "grl_graphconv_fwd: too many row tiles");
+  GRL_CHECK_ARG(tiles < 2147483647LL, "%s: too many row tiles", who_name(who));
   const DropDev d = to_dev(de);
   const bool v = g->vals != nullptr;
   // the persistent kernel (Z out, wide shapes and row-range views: only it)
@@ -848,11 +845,7 @@ static int graphconv_fused_fwd(const GrlTypedCsr* g, const XT* X, int64_t ldx, i
     launch_ws<XT, false, OT, ZT>(F, C, v, dim3((unsigned)grid), st, M, g->num_types, hs, g, X, ldx, Wf, bias, relu,
                                  out, ldo, d, ws_tiles, Z, ldz, nullptr, M, spin, status);
     GRL_LAUNCH_CHECK();
-    return graphconv_status(status, out, M, C, ldo, Z, M * ldz, st,
-                            Z16    ? WS_WHO_FWD_TRAIN_BF16_Z16
-                            : OUT16 ? (Z ? WS_WHO_FWD_TRAIN_BF16_TO_BF16 : WS_WHO_FWD_BF16_TO_BF16)
-                            : BF16 ? (Z ? WS_WHO_FWD_TRAIN_BF16 : WS_WHO_FWD_BF16)
-                                   : (Z ? WS_WHO_FWD_TRAIN : WS_WHO_FWD));
+    return graphconv_status(status, out, M, C, ldo, Z, M * ldz, st, who);
   }
   if constexpr (!BF16) {
 #define GRL_FUSED_LAUNCH(KS_)                                                                                      \
@@ -916,11 +909,22 @@ static int graphconv_fused_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, c
 // ---- the layer's dispatch: which kernels a grl_graphconv_* call runs -------
 static size_t ws_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// the two-kernel form's workspace for a graph whose GEMM path is chosen for path_rows rows
-static size_t graphconv_two_kernel_ws(const GrlTypedCsr* g, int F, int C) {
-  const int64_t K = (int64_t)segments(g) * F;
-  return ws_align((size_t)g->num_rows * (size_t)K * 4) +
-         grl_linear_fwd_ex_workspace_size(g->num_rows, (int32_t)K, C, g->path_rows);
+// The workspace of the two-kernel chain (the SpMM into an fp32 Z, then the
+// linear, whose GEMM path is chosen for path_rows rows), as byte offsets of
+// 256-B aligned regions: an fp32 Z [M, K] at 0 (z_in_ws: inference, and a
+// bf16 Z, which is rounded from it; else the caller's fp32 Z is the SpMM's
+// target), the linear's fp32 out [M, C] at lin_out (a bf16 out, rounded from
+// it), the linear's own workspace at lin_ws.  The queries answer `total`; the
+// entries take their pointers from the same struct.
+struct FwdChainLayout {
+  size_t lin_out, lin_ws, total;
+};
+static FwdChainLayout fwd_chain_layout(const GrlTypedCsr* g, int64_t K, int C, bool out16, bool z_in_ws) {
+  FwdChainLayout l;
+  l.lin_out = z_in_ws ? ws_align((size_t)g->num_rows * (size_t)K * 4) : 0;
+  l.lin_ws = l.lin_out + (out16 ? ws_align((size_t)g->num_rows * (size_t)C * 4) : 0);
+  l.total = l.lin_ws + grl_linear_fwd_ex_workspace_size(g->num_rows, (int32_t)K, C, g->path_rows);
+  return l;
 }
 
 // grl_graphconv_fwd takes the fused kernel when its arithmetic equals the
@@ -938,17 +942,23 @@ static bool fused_path(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, co
          ldx < (int64_t)((1ULL << 32) / sizeof(XT)) && (!g->split || g->split->num_heavy == 0);
 }
 
-// The bf16-output entries (grl_graphconv_fwd_bf16_to_bf16, _fwd_train_..)
-// take the one kernel where the bf16-table rule holds and out's rows take the
-// epilogue's dword stores of two columns: out 4 B-aligned, ldo even.
-static bool fused_path_out16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, const float* W, int C,
-                             const uint16_t* out, int64_t ldo) {
-  return fused_path(g, X, ldx, F, W, C) && reinterpret_cast<uintptr_t>(out) % 4 == 0 && ldo % 2 == 0;
+// The one-kernel rule of a forward entry: fused_path, and the rows the kernel
+// writes take its stores.  A bf16 out (OT = uint16_t, ldo apart a row) the
+// epilogue's dword stores of two columns: out 4 B-aligned, ldo even (an fp32
+// out is [num_rows, C] contiguous, ldo not looked at).  A Z written (train)
+// the gather waves' one store of a lane's 4 columns: 16 B-aligned for fp32, 8 B
+// for bf16 bits (K % 4 == 0 there).
+template <typename XT, typename OT, typename ZT>
+static bool fwd_one_kernel(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, const float* W, int C, const OT* out,
+                           int64_t ldo, const ZT* Z, bool train) {
+  if (std::is_same<OT, uint16_t>::value && (reinterpret_cast<uintptr_t>(out) % 4 != 0 || ldo % 2 != 0)) return false;
+  if (train && reinterpret_cast<uintptr_t>(Z) % (4 * sizeof(ZT)) != 0) return false;
+  return fused_path(g, X, ldx, F, W, C);
 }
 
-// Elsewhere they run the bf16 SpMM, the linear into an fp32 [M, C] scratch,
-// and this: dst[m, c] (ldo apart a row) = src[m, c] rounded to nearest even,
-// the kernel epilogue's conversion, so the bits are the one-kernel form's.
+// Elsewhere a bf16 out or Z is the chain's fp32 array passed through this:
+// dst[m, c] (ldo apart a row) = src[m, c] rounded to nearest even, the kernel's
+// own conversion, so the bits are the one-kernel form's.
 __global__ void round_rows_bf16_kernel(const float* __restrict__ src, int64_t M, int C, uint16_t* __restrict__ dst,
                                        int64_t ldo) {
   const int64_t n = M * C;
@@ -963,9 +973,6 @@ static int round_rows_bf16(const float* src, int64_t M, int C, uint16_t* dst, in
   return GRL_OK;
 }
 
-// the fp32 [M, C] the two-kernel form of a bf16-output entry rounds from
-static size_t out16_scratch_bytes(const GrlTypedCsr* g, int C) { return ws_align((size_t)g->num_rows * (size_t)C * 4); }
-
 // What the bf16-output entries check beyond graphconv_fwd_check (host-side,
 // before any row is looked at).
 static int out16_check(const char* who, const void* X, const void* out, int64_t ldo, int C) {
@@ -978,24 +985,22 @@ static int out16_check(const char* who, const void* X, const void* out, int64_t 
 // The data gradient of one GraphConv layer by reassociation (see grl.h):
 // dX = sum_s (A_drop,s^T G) W_s^T on the one-kernel GraphConv over the typed
 // transpose.  Eligible when the shape is (grl_graphconv_bwd_data_shape_ok) and
-// the call's pointers and plan are: a whole-range transpose, W and G rows
-// float4-aligned, no heavy-row split plan, int32 entries.
-static bool bwd_data_path(const GrlTypedCsr* gt, const float* G, int64_t ldg, int C, const float* W, int F) {
+// the call's pointers and plan are: a whole-range transpose, W 16 B-aligned,
+// every row of G (GT = float, or uint16_t: bf16 bits) aligned to the gather's
+// one load of a lane's 4 columns (16 B / 8 B) with its bytes fitting 32 bits,
+// no heavy-row split plan, int32 entries.  grl_graphconv_bwd_data_bf16 (dX
+// holds bf16 bits too, lddx apart a row) besides: the graphconv_bwd_bf16 path
+// option on, and a dX row takes the epilogue's dword stores of two columns
+// (an fp32 dX is [num_rows, F] contiguous, dX and lddx not looked at).
+template <typename GT>
+static bool bwd_data_path(const GrlTypedCsr* gt, const GT* G, int64_t ldg, int C, const float* W, int F, const GT* dX,
+                          int64_t lddx) {
+  if (std::is_same<GT, uint16_t>::value &&
+      (opt(OPT_GRAPHCONV_BWD_BF16) == 0 || reinterpret_cast<uintptr_t>(dX) % 4 != 0 || lddx % 2 != 0))
+    return false;
   return grl_graphconv_bwd_data_shape_ok(gt->num_rows, gt->num_types, gt->has_self, C, F) && gt->self_row0 == 0 &&
-         al16(W) && al16(G) && ldg % 4 == 0 && ldg < (1LL << 30) && (!gt->split || gt->split->num_heavy == 0) &&
-         gt->nnz < 2147483647LL;
-}
-
-// grl_graphconv_bwd_data_bf16 (G and dX hold bf16 bits): the same rule with
-// the alignments restated -- a G row takes the gather's 8 B load of a lane's 4
-// columns and its bytes fit 32 bits, a dX row the epilogue's dword stores of
-// two columns -- and the graphconv_bwd_bf16 path option on.
-static bool bwd_data_path_bf16(const GrlTypedCsr* gt, const uint16_t* G, int64_t ldg, int C, const float* W, int F,
-                               const uint16_t* dX, int64_t lddx) {
-  return opt(OPT_GRAPHCONV_BWD_BF16) != 0 &&
-         grl_graphconv_bwd_data_shape_ok(gt->num_rows, gt->num_types, gt->has_self, C, F) && gt->self_row0 == 0 &&
-         al16(W) && reinterpret_cast<uintptr_t>(G) % 8 == 0 && ldg % 4 == 0 && ldg < (1LL << 31) &&
-         reinterpret_cast<uintptr_t>(dX) % 4 == 0 && lddx % 2 == 0 && (!gt->split || gt->split->num_heavy == 0) &&
+         al16(W) && reinterpret_cast<uintptr_t>(G) % (4 * sizeof(GT)) == 0 && ldg % 4 == 0 &&
+         ldg < (int64_t)((1ULL << 32) / sizeof(GT)) && (!gt->split || gt->split->num_heavy == 0) &&
          gt->nnz < 2147483647LL;
 }
 
@@ -1030,69 +1035,73 @@ static int spmm_fwd(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_
   return grl_typed_spmm_fwd_bf16(g, X, ldx, F, 0, Z, (int64_t)segments(g) * F, F, de, stream);
 }
 
-// The rule of an entry with out of OT (float: [num_rows, C] contiguous, ldo
-// not looked at; uint16_t: bf16 bits, ldo apart a row).
-template <typename XT, typename OT>
-static bool fwd_one_kernel(const GrlTypedCsr* g, const XT* X, int64_t ldx, int F, const float* W, int C, const OT* out,
-                           int64_t ldo) {
-  if constexpr (std::is_same<OT, uint16_t>::value)
-    return fused_path_out16(g, X, ldx, F, W, C, out, ldo);
-  else
-    return fused_path(g, X, ldx, F, W, C);
-}
-
-template <typename XT, typename OT = float>
-static size_t graphconv_fwd_workspace_query(const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F, const float* W,
-                                            int32_t C, const OT* out = nullptr, int64_t ldo = 0) {
-  if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0) return 0;
+// What a forward entry's workspace query answers: W's planes where the call
+// takes one kernel, else the chain's total.  TRAIN: the entry writes Z.
+template <bool TRAIN, typename XT, typename OT, typename ZT>
+static size_t graphconv_fwd_query(const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F, const float* W, int32_t C,
+                                  const OT* out, int64_t ldo, const ZT* Z) {
+  constexpr bool OUT16 = std::is_same<OT, uint16_t>::value;
+  if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0 || (OUT16 && ldo < C)) return 0;
   const int64_t K = (int64_t)segments(g) * F;
   if (K > 2147483647LL) return 0;
-  if (fwd_one_kernel(g, X, ldx, F, W, C, out, ldo)) return graphconv_fused_ws_bytes(K, C);
-  return graphconv_two_kernel_ws(g, F, C) + (std::is_same<OT, uint16_t>::value ? out16_scratch_bytes(g, C) : 0);
+  if (fwd_one_kernel(g, X, ldx, F, W, C, out, ldo, Z, TRAIN)) return graphconv_fused_ws_bytes(K, C);
+  return fwd_chain_layout(g, K, C, OUT16, !TRAIN || std::is_same<ZT, uint16_t>::value).total;
 }
 
-template <typename XT, typename OT = float>
-static int graphconv_fwd(const char* who, const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F, const float* W,
-                         const float* bias, int32_t C, int32_t relu, OT* out, int64_t ldo, const GrlDropEdge* de,
-                         void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+// Every grl_graphconv_fwd* entry.  XT, OT, ZT: float, or uint16_t for bf16 bits
+// (a bf16 out over a bf16 table only, a bf16 Z with a bf16 out only; W and bias
+// are fp32).  TRAIN: Z [num_rows, segments * F] is written too; else Z is NULL.
+// One kernel where the rule holds and the workspace takes W's planes; else the
+// two-kernel chain over fwd_chain_layout; else, for inference over an fp32
+// table, Z in row chunks.
+template <bool TRAIN, typename XT, typename OT, typename ZT>
+static int graphconv_fwd_run(const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F, const float* W,
+                             const float* bias, int32_t C, int32_t relu, OT* out, int64_t ldo, ZT* Z,
+                             const GrlDropEdge* de, void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  constexpr bool BF16 = std::is_same<XT, uint16_t>::value;
   constexpr bool OUT16 = std::is_same<OT, uint16_t>::value;
+  constexpr bool Z16 = std::is_same<ZT, uint16_t>::value;
+  static_assert(TRAIN || !Z16, "inference passes a NULL float* Z");
+  constexpr int who_bit = ws_who_fwd(BF16, OUT16, Z16, TRAIN);
+  const char* const who = who_name(who_bit);
   TraceRange trace_(who);
   int32_t K = 0;
-  int rc = graphconv_fwd_check(who, g, X, ldx, F, W, C, out != nullptr, workspace, &K);
+  int rc = graphconv_fwd_check(who, g, X, ldx, F, W, C, out && (Z || !TRAIN), workspace, &K);
   if (rc) return rc;
   if constexpr (OUT16) {
     rc = out16_check(who, X, out, ldo, C);
     if (rc) return rc;
   }
-  if (g->num_rows == 0) return rc;
+  if constexpr (Z16)
+    GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(Z) % 2 == 0, "%s: Z holds 2-byte elements and must be 2-B aligned", who);
+  if (g->num_rows == 0) return GRL_OK;
   const int64_t M = g->num_rows;
   hipStream_t st = as_stream(stream);
   char* ws = static_cast<char*>(workspace);
-  if (fwd_one_kernel(g, X, ldx, F, W, C, out, ldo) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, ldo, de, ws, st);  // one kernel: Z stays on the CU
-  const size_t scratch = OUT16 ? out16_scratch_bytes(g, C) : 0;
-  const size_t need = graphconv_two_kernel_ws(g, F, C) + scratch;
-  if (ws && workspace_bytes >= need) {
-    // whole graph: Z in the workspace, then the linear (its workspace behind Z; a bf16 out: into an fp32
-    // [M, C] between the two, rounded into out's rows afterwards)
-    const size_t zfull = ws_align((size_t)M * (size_t)K * 4);
-    float* Z = reinterpret_cast<float*>(ws);
-    rc = spmm_fwd(g, X, ldx, F, Z, de, stream);
-    if (rc) return rc;
-    float* lin_out;
-    if constexpr (OUT16)
-      lin_out = reinterpret_cast<float*>(ws + zfull);
-    else
-      lin_out = out;
-    rc = grl_linear_fwd_ex(Z, K, W, 0, bias, lin_out, M, K, C, relu, g->path_rows, ws + zfull + scratch,
-                           workspace_bytes - zfull - scratch, stream);
+  if (fwd_one_kernel(g, X, ldx, F, W, C, out, ldo, Z, TRAIN) && ws && workspace_bytes >= graphconv_fused_ws_bytes(K, C))
+    return graphconv_fused_fwd(who_bit, g, X, ldx, F, W, bias, C, relu, out, ldo, de, ws, st, Z);  // Z stays on the CU
+  const FwdChainLayout l = fwd_chain_layout(g, K, C, OUT16, !TRAIN || Z16);
+  // (the fp32-out training entries put nothing of their own in the workspace: the linear takes all of it and
+  // picks its arithmetic from the bytes it is given, so they refuse nothing here)
+  if ((TRAIN && !OUT16) || (ws && workspace_bytes >= l.total)) {
+    float* Z32 = reinterpret_cast<float*>(ws);  // the SpMM's target: the workspace's head, or the caller's fp32 Z
+    if constexpr (TRAIN && !Z16) Z32 = Z;
+    float* lin_out = reinterpret_cast<float*>(ws + l.lin_out);
+    if constexpr (!OUT16) lin_out = out;
+    rc = spmm_fwd(g, X, ldx, F, Z32, de, stream);
+    if (!rc)
+      rc = grl_linear_fwd_ex(Z32, K, W, 0, bias, lin_out, M, K, C, relu, g->path_rows, ws + l.lin_ws,
+                             workspace_bytes - l.lin_ws, stream);
     if constexpr (OUT16) {
       if (!rc) rc = round_rows_bf16(lin_out, M, C, out, ldo, st);
     }
+    if constexpr (Z16) {
+      if (!rc) rc = round_rows_bf16(Z32, M, K, Z, (int64_t)K, st);
+    }
     return rc;
   }
-  if constexpr (std::is_same<XT, uint16_t>::value) {
-    GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);  // no row-chunked form
+  if constexpr (TRAIN || BF16) {
+    GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, l.total);  // no row-chunked form
   } else {
     // Row chunks: Z for R rows at a time (bounded memory), on the x6 GEMM only,
     // whose per-element arithmetic does not depend on M -- so the result is
@@ -1108,61 +1117,40 @@ static int graphconv_fwd(const char* who, const GrlTypedCsr* g, const XT* X, int
     if (R < LB_M)
       GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu holds fewer than %d rows of Z", who, workspace_bytes, LB_M);
     uint16_t* planes = reinterpret_cast<uint16_t*>(ws);
-    float* Z = reinterpret_cast<float*>(ws + planes_bytes);
+    float* Zr = reinterpret_cast<float*>(ws + planes_bytes);
     rc = x6_split_w(W, K, C, planes, st);
     for (int64_t r0 = 0; r0 < M && !rc; r0 += R) {
       const int64_t rows = std::min<int64_t>(R, M - r0);
-      rc = spmm_fwd_rows(g, r0, rows, X, ldx, F, Z, de, st);
-      if (!rc) rc = x6_gemm_rows(Z, rows, K, planes, C, bias, relu, out + r0 * C, st);
+      rc = spmm_fwd_rows(g, r0, rows, X, ldx, F, Zr, de, st);
+      if (!rc) rc = x6_gemm_rows(Zr, rows, K, planes, C, bias, relu, out + r0 * C, st);
     }
     return rc;
   }
 }
 
-template <typename XT, typename OT = float>
-static int graphconv_fwd_train(const char* who, const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F,
-                               const float* W, const float* bias, int32_t C, int32_t relu, OT* out, int64_t ldo,
-                               float* Z, const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
-                               grl_stream_t stream) {
-  TraceRange trace_(who);
-  int32_t K = 0;
-  int rc = graphconv_fwd_check(who, g, X, ldx, F, W, C, out && Z, workspace, &K);
-  if (rc) return rc;
-  if constexpr (std::is_same<OT, uint16_t>::value) {
-    rc = out16_check(who, X, out, ldo, C);
-    if (rc) return rc;
-  }
-  if (g->num_rows == 0) return rc;
-  if (fwd_one_kernel(g, X, ldx, F, W, C, out, ldo) && al16(Z) && workspace &&
-      workspace_bytes >= graphconv_fused_ws_bytes(K, C))
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, ldo, de, workspace, as_stream(stream), Z);
-  if constexpr (std::is_same<OT, uint16_t>::value) {
-    // the linear into an fp32 [M, C] at the head of the workspace, rounded into out's rows
-    const size_t scratch = out16_scratch_bytes(g, C);
-    const size_t need = scratch + grl_linear_fwd_ex_workspace_size(g->num_rows, K, C, g->path_rows);
-    if (!workspace || workspace_bytes < need)
-      GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
-    float* lin_out = static_cast<float*>(workspace);
-    rc = spmm_fwd(g, X, ldx, F, Z, de, stream);
-    if (!rc)
-      rc = grl_linear_fwd_ex(Z, K, W, 0, bias, lin_out, g->num_rows, K, C, relu, g->path_rows,
-                             static_cast<char*>(workspace) + scratch, workspace_bytes - scratch, stream);
-    return rc ? rc : round_rows_bf16(lin_out, g->num_rows, C, out, ldo, as_stream(stream));
-  } else {
-    rc = spmm_fwd(g, X, ldx, F, Z, de, stream);
-    return rc ? rc : grl_linear_fwd_ex(Z, K, W, 0, bias, out, g->num_rows, K, C, relu, g->path_rows, workspace,
-                                       workspace_bytes, stream);
-  }
-}
+static float* const NO_Z = nullptr;  // inference: no Z is written
 
 extern "C" size_t grl_graphconv_fwd_workspace_query(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F,
                                                    const float* W, int32_t C) {
-  return graphconv_fwd_workspace_query(g, X, ldx, F, W, C);
+  return graphconv_fwd_query<false>(g, X, ldx, F, W, C, (const float*)nullptr, (int64_t)C, NO_Z);
 }
 
 extern "C" size_t grl_graphconv_fwd_bf16_workspace_query(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx,
                                                         int32_t F, const float* W, int32_t C) {
-  return graphconv_fwd_workspace_query(g, X, ldx, F, W, C);
+  return graphconv_fwd_query<false>(g, X, ldx, F, W, C, (const float*)nullptr, (int64_t)C, NO_Z);
+}
+
+extern "C" size_t grl_graphconv_fwd_bf16_to_bf16_workspace_query(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx,
+                                                                int32_t F, const float* W, int32_t C,
+                                                                const uint16_t* out, int64_t ldo) {
+  return graphconv_fwd_query<false>(g, X, ldx, F, W, C, out, ldo, NO_Z);
+}
+
+extern "C" size_t grl_graphconv_fwd_train_bf16_z16_workspace_query(const GrlTypedCsr* g, const uint16_t* X,
+                                                                  int64_t ldx, int32_t F, const float* W, int32_t C,
+                                                                  const uint16_t* out, int64_t ldo,
+                                                                  const uint16_t* Z) {
+  return graphconv_fwd_query<true>(g, X, ldx, F, W, C, out, ldo, Z);
 }
 
 extern "C" size_t grl_graphconv_fwd_workspace_size(int64_t num_rows, int32_t num_types, int32_t has_self, int32_t F,
@@ -1176,112 +1164,53 @@ extern "C" size_t grl_graphconv_fwd_workspace_size(int64_t num_rows, int32_t num
 extern "C" int grl_graphconv_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
                                  const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
                                  void* workspace, size_t workspace_bytes, grl_stream_t stream) {
-  return graphconv_fwd("grl_graphconv_fwd", g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, de, workspace,
-                       workspace_bytes, stream);
+  return graphconv_fwd_run<false>(g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, NO_Z, de, workspace,
+                                  workspace_bytes, stream);
 }
 
 extern "C" int grl_graphconv_fwd_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F, const float* W,
                                       const float* bias, int32_t C, int32_t relu, float* out, const GrlDropEdge* de,
                                       void* workspace, size_t workspace_bytes, grl_stream_t stream) {
-  return graphconv_fwd("grl_graphconv_fwd_bf16", g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, de, workspace,
-                       workspace_bytes, stream);
-}
-
-extern "C" int grl_graphconv_fwd_train(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
-                                       const float* bias, int32_t C, int32_t relu, float* out, float* Z,
-                                       const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
-                                       grl_stream_t stream) {
-  return graphconv_fwd_train("grl_graphconv_fwd_train", g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, Z, de,
-                             workspace, workspace_bytes, stream);
-}
-
-extern "C" int grl_graphconv_fwd_train_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
-                                            const float* W, const float* bias, int32_t C, int32_t relu, float* out,
-                                            float* Z, const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
-                                            grl_stream_t stream) {
-  return graphconv_fwd_train("grl_graphconv_fwd_train_bf16", g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, Z, de,
-                             workspace, workspace_bytes, stream);
-}
-
-extern "C" size_t grl_graphconv_fwd_bf16_to_bf16_workspace_query(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx,
-                                                                int32_t F, const float* W, int32_t C,
-                                                                const uint16_t* out, int64_t ldo) {
-  if (ldo < C) return 0;
-  return graphconv_fwd_workspace_query(g, X, ldx, F, W, C, out, ldo);
+  return graphconv_fwd_run<false>(g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, NO_Z, de, workspace,
+                                  workspace_bytes, stream);
 }
 
 extern "C" int grl_graphconv_fwd_bf16_to_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
                                               const float* W, const float* bias, int32_t C, int32_t relu,
                                               uint16_t* out, int64_t ldo, const GrlDropEdge* de, void* workspace,
                                               size_t workspace_bytes, grl_stream_t stream) {
-  return graphconv_fwd("grl_graphconv_fwd_bf16_to_bf16", g, X, ldx, F, W, bias, C, relu, out, ldo, de, workspace,
-                       workspace_bytes, stream);
+  return graphconv_fwd_run<false>(g, X, ldx, F, W, bias, C, relu, out, ldo, NO_Z, de, workspace, workspace_bytes,
+                                  stream);
+}
+
+extern "C" int grl_graphconv_fwd_train(const GrlTypedCsr* g, const float* X, int64_t ldx, int32_t F, const float* W,
+                                       const float* bias, int32_t C, int32_t relu, float* out, float* Z,
+                                       const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
+                                       grl_stream_t stream) {
+  return graphconv_fwd_run<true>(g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, Z, de, workspace, workspace_bytes,
+                                 stream);
+}
+
+extern "C" int grl_graphconv_fwd_train_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+                                            const float* W, const float* bias, int32_t C, int32_t relu, float* out,
+                                            float* Z, const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
+                                            grl_stream_t stream) {
+  return graphconv_fwd_run<true>(g, X, ldx, F, W, bias, C, relu, out, (int64_t)C, Z, de, workspace, workspace_bytes,
+                                 stream);
 }
 
 extern "C" int grl_graphconv_fwd_train_bf16_to_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
                                                     const float* W, const float* bias, int32_t C, int32_t relu,
                                                     uint16_t* out, int64_t ldo, float* Z, const GrlDropEdge* de,
                                                     void* workspace, size_t workspace_bytes, grl_stream_t stream) {
-  return graphconv_fwd_train("grl_graphconv_fwd_train_bf16_to_bf16", g, X, ldx, F, W, bias, C, relu, out, ldo, Z, de,
-                             workspace, workspace_bytes, stream);
-}
-
-// ---- grl_graphconv_fwd_train_bf16_z16: the bf16-output training forward
-// whose Z holds bf16 bits too.  One kernel where the bf16-output rule holds and
-// a Z row takes the gather waves' 8 B stores (K % 4 == 0 there); elsewhere the
-// bf16 SpMM into an fp32 Z at the head of the workspace, the linear into an
-// fp32 [M, C] behind it, and the rounding pass over each.
-static bool z16_one_kernel(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, const float* W, int C,
-                           const uint16_t* out, int64_t ldo, const uint16_t* Z) {
-  return fused_path_out16(g, X, ldx, F, W, C, out, ldo) && reinterpret_cast<uintptr_t>(Z) % 8 == 0;
-}
-
-static size_t z16_two_kernel_ws(const GrlTypedCsr* g, int64_t K, int C) {
-  return ws_align((size_t)g->num_rows * (size_t)K * 4) + out16_scratch_bytes(g, C) +
-         grl_linear_fwd_ex_workspace_size(g->num_rows, (int32_t)K, C, g->path_rows);
-}
-
-extern "C" size_t grl_graphconv_fwd_train_bf16_z16_workspace_query(const GrlTypedCsr* g, const uint16_t* X,
-                                                                  int64_t ldx, int32_t F, const float* W, int32_t C,
-                                                                  const uint16_t* out, int64_t ldo,
-                                                                  const uint16_t* Z) {
-  if (!g || g->num_rows <= 0 || g->num_types < 1 || F <= 0 || C <= 0 || ldo < C) return 0;
-  const int64_t K = (int64_t)segments(g) * F;
-  if (K > 2147483647LL) return 0;
-  if (z16_one_kernel(g, X, ldx, F, W, C, out, ldo, Z)) return graphconv_fused_ws_bytes(K, C);
-  return z16_two_kernel_ws(g, K, C);
+  return graphconv_fwd_run<true>(g, X, ldx, F, W, bias, C, relu, out, ldo, Z, de, workspace, workspace_bytes, stream);
 }
 
 extern "C" int grl_graphconv_fwd_train_bf16_z16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
                                                 const float* W, const float* bias, int32_t C, int32_t relu,
                                                 uint16_t* out, int64_t ldo, uint16_t* Z, const GrlDropEdge* de,
                                                 void* workspace, size_t workspace_bytes, grl_stream_t stream) {
-  const char* const who = "grl_graphconv_fwd_train_bf16_z16";
-  TraceRange trace_(who);
-  int32_t K = 0;
-  int rc = graphconv_fwd_check(who, g, X, ldx, F, W, C, out && Z, workspace, &K);
-  if (rc) return rc;
-  rc = out16_check(who, X, out, ldo, C);
-  if (rc) return rc;
-  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(Z) % 2 == 0, "%s: Z holds 2-byte elements and must be 2-B aligned", who);
-  if (g->num_rows == 0) return rc;
-  const int64_t M = g->num_rows;
-  hipStream_t st = as_stream(stream);
-  if (z16_one_kernel(g, X, ldx, F, W, C, out, ldo, Z) && workspace &&
-      workspace_bytes >= graphconv_fused_ws_bytes(K, C))
-    return graphconv_fused_fwd(g, X, ldx, F, W, bias, C, relu, out, ldo, de, workspace, st, Z);
-  const size_t zfull = ws_align((size_t)M * (size_t)K * 4), scratch = out16_scratch_bytes(g, C);
-  const size_t need = z16_two_kernel_ws(g, K, C);
-  if (!workspace || workspace_bytes < need) GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
-  char* ws = static_cast<char*>(workspace);
-  float* Z32 = reinterpret_cast<float*>(ws);
-  float* lin_out = reinterpret_cast<float*>(ws + zfull);
-  rc = spmm_fwd(g, X, ldx, F, Z32, de, stream);
-  if (!rc)
-    rc = grl_linear_fwd_ex(Z32, K, W, 0, bias, lin_out, M, K, C, relu, g->path_rows, ws + zfull + scratch,
-                           workspace_bytes - zfull - scratch, stream);
-  if (!rc) rc = round_rows_bf16(lin_out, M, C, out, ldo, st);
-  return rc ? rc : round_rows_bf16(Z32, M, K, Z, (int64_t)K, st);
+  return graphconv_fwd_run<true>(g, X, ldx, F, W, bias, C, relu, out, ldo, Z, de, workspace, workspace_bytes, stream);
 }
 
 extern "C" int32_t grl_graphconv_bwd_data_shape_ok(int64_t rows, int32_t num_types, int32_t has_self, int32_t C,
@@ -1291,71 +1220,72 @@ extern "C" int32_t grl_graphconv_bwd_data_shape_ok(int64_t rows, int32_t num_typ
          F % 4 == 0 && K <= 2147483647LL;
 }
 
-extern "C" size_t grl_graphconv_bwd_data_workspace_query(const GrlTypedCsr* gt, const float* G, int64_t ldg, int32_t C,
-                                                        const float* W, int32_t F) {
-  if (!gt || gt->num_rows <= 0 || gt->num_types < 1 || C <= 0 || F <= 0) return 0;
-  return bwd_data_path(gt, G, ldg, C, W, F) ? graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F) : 0;
-}
-
-extern "C" int grl_graphconv_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const float* G, int64_t ldg,
-                                      int64_t g_rows, int32_t C, const float* W, int32_t F, float* dX, float* G_agg,
-                                      const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
-                                      grl_stream_t stream) {
-  TraceRange trace_("grl_graphconv_bwd_data");
-  GRL_CHECK_ARG(gt != nullptr, "grl_graphconv_bwd_data: graph is NULL");
-  GRL_CHECK_ARG(gt->num_rows >= 0 && gt->num_types >= 1 && gt->num_types <= 63,
-                "grl_graphconv_bwd_data: num_types must be in [1, 63] (got %d)", gt->num_types);
-  GRL_CHECK_ARG(C > 0 && ldg >= C && F > 0 && g_rows >= 0 && g_rows <= gt->num_rows,
-                "grl_graphconv_bwd_data: need C > 0, ldg >= C, F > 0, 0 <= g_rows <= num_rows");
-  if (gt->num_rows == 0) return GRL_OK;
-  // (an empty node-range shard: no G rows and no entries, so its empty G is never read)
-  GRL_CHECK_ARG((G || (g_rows == 0 && gt->nnz == 0)) && W && dX && gt->rowptr && (gt->nnz == 0 || (gt->colidx && eid)),
-                "grl_graphconv_bwd_data: NULL pointer");
-  if (!bwd_data_path(gt, G, ldg, C, W, F))
-    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_graphconv_bwd_data: shape outside the one-kernel path (C %d, F %d, L %d, rows "
-             "%lld; see grl_graphconv_bwd_data_workspace_query)", C, F, gt->num_types, (long long)gt->num_rows);
-  const size_t need = graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F);
-  if (!workspace || !al16(workspace) || workspace_bytes < need)
-    GRL_FAIL(GRL_E_WORKSPACE, "grl_graphconv_bwd_data: workspace %zu < %zu (16-B aligned)", workspace_bytes, need);
-  return graphconv_fused_bwd_data(gt, eid, G, ldg, g_rows, C, W, F, dX, (int64_t)F, G_agg, de, workspace,
-                                  as_stream(stream));
-}
-
-extern "C" size_t grl_graphconv_bwd_data_bf16_workspace_query(const GrlTypedCsr* gt, const uint16_t* G, int64_t ldg,
-                                                             int32_t C, const float* W, int32_t F, const uint16_t* dX,
-                                                             int64_t lddx) {
-  if (!gt || gt->num_rows <= 0 || gt->num_types < 1 || C <= 0 || F <= 0 || !dX || lddx < F || ldg < C) return 0;
-  return bwd_data_path_bf16(gt, G, ldg, C, W, F, dX, lddx) ? graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F) : 0;
-}
-
-extern "C" int grl_graphconv_bwd_data_bf16(const GrlTypedCsr* gt, const int32_t* eid, const uint16_t* G, int64_t ldg,
-                                           int64_t g_rows, int32_t C, const float* W, int32_t F, uint16_t* dX,
-                                           int64_t lddx, float* G_agg, const GrlDropEdge* de, void* workspace,
-                                           size_t workspace_bytes, grl_stream_t stream) {
-  const char* const who = "grl_graphconv_bwd_data_bf16";
+// Both data-gradient entries.  GT = float: G fp32, dX [num_rows, F] contiguous
+// (lddx = F); GT = uint16_t: both hold bf16 bits, dX's rows lddx apart, which
+// has checks of its own (2-byte elements, strided dword stores into dX, the
+// gather waves' 16 B stores into G_agg).
+template <typename GT>
+static int graphconv_bwd_data_run(const GrlTypedCsr* gt, const int32_t* eid, const GT* G, int64_t ldg, int64_t g_rows,
+                                  int32_t C, const float* W, int32_t F, GT* dX, int64_t lddx, float* G_agg,
+                                  const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
+                                  grl_stream_t stream) {
+  constexpr bool BF16 = std::is_same<GT, uint16_t>::value;
+  const char* const who = who_name(BF16 ? WS_WHO_BWD_DATA_BF16 : WS_WHO_BWD_DATA);
   TraceRange trace_(who);
   GRL_CHECK_ARG(gt != nullptr, "%s: graph is NULL", who);
   GRL_CHECK_ARG(gt->num_rows >= 0 && gt->num_types >= 1 && gt->num_types <= 63,
                 "%s: num_types must be in [1, 63] (got %d)", who, gt->num_types);
   GRL_CHECK_ARG(C > 0 && ldg >= C && F > 0 && g_rows >= 0 && g_rows <= gt->num_rows,
                 "%s: need C > 0, ldg >= C, F > 0, 0 <= g_rows <= num_rows", who);
-  GRL_CHECK_ARG(lddx >= F, "%s: need lddx >= F (lddx=%lld F=%d)", who, (long long)lddx, F);
-  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(G) % 2 == 0 && reinterpret_cast<uintptr_t>(dX) % 2 == 0,
-                "%s: G and dX hold 2-byte elements and must be 2-B aligned", who);
+  if constexpr (BF16) {
+    GRL_CHECK_ARG(lddx >= F, "%s: need lddx >= F (lddx=%lld F=%d)", who, (long long)lddx, F);
+    GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(G) % 2 == 0 && reinterpret_cast<uintptr_t>(dX) % 2 == 0,
+                  "%s: G and dX hold 2-byte elements and must be 2-B aligned", who);
+  }
   if (gt->num_rows == 0) return GRL_OK;
   // (an empty node-range shard: no G rows and no entries, so its empty G is never read)
   GRL_CHECK_ARG((G || (g_rows == 0 && gt->nnz == 0)) && W && dX && gt->rowptr && (gt->nnz == 0 || (gt->colidx && eid)),
                 "%s: NULL pointer", who);
-  GRL_CHECK_ARG(al16(G_agg), "%s: G_agg must be 16-B aligned (the gather waves' 16 B row stores)", who);
-  if (!bwd_data_path_bf16(gt, G, ldg, C, W, F, dX, lddx))
+  if constexpr (BF16)
+    GRL_CHECK_ARG(al16(G_agg), "%s: G_agg must be 16-B aligned (the gather waves' 16 B row stores)", who);
+  if (!bwd_data_path<GT>(gt, G, ldg, C, W, F, dX, lddx))
     GRL_FAIL(GRL_E_UNSUPPORTED, "%s: outside the one-kernel path (C %d, F %d, L %d, rows %lld, the operands' "
-             "alignment or the graphconv_bwd_bf16 option; see grl_graphconv_bwd_data_bf16_workspace_query)", who, C, F,
-             gt->num_types, (long long)gt->num_rows);
+             "alignment%s; see %s_workspace_query)", who, C, F, gt->num_types, (long long)gt->num_rows,
+             BF16 ? " or the graphconv_bwd_bf16 option" : "", who);
   const size_t need = graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F);
   if (!workspace || !al16(workspace) || workspace_bytes < need)
     GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu (16-B aligned)", who, workspace_bytes, need);
-  return graphconv_fused_bwd_data(gt, eid, G, ldg, g_rows, C, W, F, dX, lddx, G_agg, de, workspace,
-                                  as_stream(stream));
+  return graphconv_fused_bwd_data(gt, eid, G, ldg, g_rows, C, W, F, dX, lddx, G_agg, de, workspace, as_stream(stream));
+}
+
+extern "C" size_t grl_graphconv_bwd_data_workspace_query(const GrlTypedCsr* gt, const float* G, int64_t ldg, int32_t C,
+                                                        const float* W, int32_t F) {
+  if (!gt || gt->num_rows <= 0 || gt->num_types < 1 || C <= 0 || F <= 0) return 0;
+  return bwd_data_path<float>(gt, G, ldg, C, W, F, nullptr, F) ? graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F)
+                                                              : 0;
+}
+
+extern "C" int grl_graphconv_bwd_data(const GrlTypedCsr* gt, const int32_t* eid, const float* G, int64_t ldg,
+                                      int64_t g_rows, int32_t C, const float* W, int32_t F, float* dX, float* G_agg,
+                                      const GrlDropEdge* de, void* workspace, size_t workspace_bytes,
+                                      grl_stream_t stream) {
+  return graphconv_bwd_data_run(gt, eid, G, ldg, g_rows, C, W, F, dX, (int64_t)F, G_agg, de, workspace,
+                                workspace_bytes, stream);
+}
+
+extern "C" size_t grl_graphconv_bwd_data_bf16_workspace_query(const GrlTypedCsr* gt, const uint16_t* G, int64_t ldg,
+                                                             int32_t C, const float* W, int32_t F, const uint16_t* dX,
+                                                             int64_t lddx) {
+  if (!gt || gt->num_rows <= 0 || gt->num_types < 1 || C <= 0 || F <= 0 || !dX || lddx < F || ldg < C) return 0;
+  return bwd_data_path(gt, G, ldg, C, W, F, dX, lddx) ? graphconv_fused_ws_bytes((int64_t)segments(gt) * C, F) : 0;
+}
+
+extern "C" int grl_graphconv_bwd_data_bf16(const GrlTypedCsr* gt, const int32_t* eid, const uint16_t* G, int64_t ldg,
+                                           int64_t g_rows, int32_t C, const float* W, int32_t F, uint16_t* dX,
+                                           int64_t lddx, float* G_agg, const GrlDropEdge* de, void* workspace,
+                                           size_t workspace_bytes, grl_stream_t stream) {
+  return graphconv_bwd_data_run(gt, eid, G, ldg, g_rows, C, W, F, dX, lddx, G_agg, de, workspace, workspace_bytes,
+                                stream);
 }
 
 namespace grl {

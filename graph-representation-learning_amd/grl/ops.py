@@ -57,6 +57,15 @@ def _bf16_suffix(X2: torch.Tensor, out: torch.Tensor = None) -> str:
     return "_bf16_to_bf16" if out is not None and out.dtype == torch.bfloat16 else "_bf16"
 
 
+def _graphconv_fwd_call(entry: str, csr, X2, F, Wc, bc, relu: bool, out, Z, graph, ws_bytes: int):
+    """One grl_graphconv_fwd* call on a new workspace (ldo behind a bfloat16 out, Z behind that when training)."""
+    ws = _workspace(ws_bytes, X2.device)
+    call(entry, ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc), Wc.shape[1], int(relu),
+         out.data_ptr(), *([out.stride(0)] if out.dtype == torch.bfloat16 else []),
+         *([Z.data_ptr()] if Z is not None else []), _de_ref(graph), _ptr(ws), ws_bytes,
+         current_stream_handle(X2.device))
+
+
 def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: bool = False):
     """The checked operands of a forward over `graph` -- (X2, F, Wc, bc, out,
     Z): the features' 2-D row view and width, the contiguous weights
@@ -906,17 +915,13 @@ def graph_conv_fwd_train(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=
     K, C = Wc.shape
     csr = graph.csr_c(F)
     ws_bytes = _lib.lib().grl_linear_fwd_ex_workspace_size(graph.num_rows, K, C, graph.path_rows)
-    sfx = _bf16_suffix(X2, out)
-    args = [ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc), C, int(relu), out.data_ptr()]
     if out.dtype == torch.bfloat16:
-        args.append(out.stride(0))
         full = _lib.lib().grl_graphconv_fwd_bf16_to_bf16_workspace_query(
             ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), C, out.data_ptr(), out.stride(0))
         if full >= graph.num_rows * K * 4 or Z.data_ptr() % 16:  # two kernels: the linear's fp32 [num_rows, C]
             ws_bytes += (graph.num_rows * C * 4 + 255) // 256 * 256
-    ws = _workspace(ws_bytes, X.device)
-    call("grl_graphconv_fwd_train" + sfx, *args, Z.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes,
-         current_stream_handle(X.device))
+    _graphconv_fwd_call("grl_graphconv_fwd_train" + _bf16_suffix(X2, out), csr, X2, F, Wc, bc, relu, out, Z, graph,
+                        ws_bytes)
     return out, Z
 
 
@@ -948,10 +953,7 @@ def _graph_conv_fwd_train_z16(who: str, X, graph, W, b, relu: bool, out, Z):
     ws_bytes = _lib.lib().grl_graphconv_fwd_train_bf16_z16_workspace_query(
         ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), C, out.data_ptr(), out.stride(0),
         Z.data_ptr())
-    ws = _workspace(ws_bytes, X.device)
-    call("grl_graphconv_fwd_train_bf16_z16", ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc),
-         C, int(relu), out.data_ptr(), out.stride(0), Z.data_ptr(), _de_ref(graph), _ptr(ws), ws_bytes,
-         current_stream_handle(X.device))
+    _graphconv_fwd_call("grl_graphconv_fwd_train_bf16_z16", csr, X2, F, Wc, bc, relu, out, Z, graph, ws_bytes)
     return out, Z
 
 
@@ -975,15 +977,12 @@ def graph_conv_infer(X: torch.Tensor, graph: TypedGraph, W: torch.Tensor, b=None
     C = Wc.shape[1]
     csr = graph.csr_c(F)
     sfx = _bf16_suffix(X2, out)
-    out16 = out.dtype == torch.bfloat16
-    out_args = [out.data_ptr(), out.stride(0)] if out16 else [out.data_ptr()]
+    out_args = [out.data_ptr(), out.stride(0)] if out.dtype == torch.bfloat16 else []
     # the fused one-kernel path needs only W's planes; else Z whole (the bf16-out rule also looks at out's rows)
     query = getattr(_lib.lib(), f"grl_graphconv_fwd{sfx}_workspace_query")
-    full = query(ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), C, *(out_args if out16 else []))
+    full = query(ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), C, *out_args)
     ws_bytes = full if max_workspace_bytes is None else min(full, int(max_workspace_bytes))
-    ws = _workspace(ws_bytes, X.device)
-    call("grl_graphconv_fwd" + sfx, ctypes.byref(csr), X2.data_ptr(), X2.stride(0), F, Wc.data_ptr(), _ptr(bc), C,
-         int(relu), *out_args, _de_ref(graph), _ptr(ws), ws_bytes, current_stream_handle(X.device))
+    _graphconv_fwd_call("grl_graphconv_fwd" + sfx, csr, X2, F, Wc, bc, relu, out, None, graph, ws_bytes)
     return out
 
 
