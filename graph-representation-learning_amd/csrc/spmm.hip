@@ -23,8 +23,8 @@
 //    are deterministic and equal the oracle's fmaf chain;
 //  * type-segment boundaries are wave-uniform scalar compares, so a row's
 //    edges of all types stream through one loop (no per-type round trip).
-// The forward also reads a table of bf16 bits (grl_typed_spmm_fwd_bf16): its
-// kernels follow the fp32 ones below, and the two share the host code.
+// The forward also reads a table of bf16 bits (grl_typed_spmm_fwd_bf16), and both directions run with bf16 on
+// both sides (_fwd_bf16_to_bf16, _bwd_bf16): those kernels follow the fp32 ones below and share the host code.
 #include <climits>
 
 #include <hipcub/hipcub.hpp>
@@ -821,6 +821,368 @@ __global__ __launch_bounds__(256) void spmm_bf16_fixup_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------
+// bf16 on both sides (grl_typed_spmm_fwd_bf16_to_bf16, grl_typed_spmm_bwd_bf16)
+// ---------------------------------------------------------------------------
+// The gathered rows are bf16 bits and so is the output:
+//  BWD = false: the contract of spmm_bf16_kernel / spmm_bf16_pair_kernel with
+//    Z stored as bf16 -- every segment's fp32 accumulators rounded once, to
+//    nearest even (cvt_pk_bf16), at the store;
+//  BWD = true : the contract of spmm_kernel<..., BWD = true> over a bf16 dZ
+//    (ptr = colptr, idx = zrow into dZ viewed as rows of lds = zseg elements,
+//    ids = edge_base + eid[e], one segment per item, the self term -- the
+//    column's own dZ row -- first), dX stored as bf16, rounded once.
+// The accumulators and the chunk partials of heavy rows stay fp32: a chunk
+// item stores its fp32 partial row as the kernels above do, and the fixup
+// below does the one rounding of a heavy segment or column.  Siblings of the
+// fp32-output kernels, not instances of them: those keep their machine code.
+using u4v = __attribute__((ext_vector_type(4))) uint32_t;
+__device__ __forceinline__ void vstore(uint16_t* p, const float (&v)[8]) {
+  const u4v t = {cvt_pk_bf16(v[0], v[1]), cvt_pk_bf16(v[2], v[3]), cvt_pk_bf16(v[4], v[5]), cvt_pk_bf16(v[6], v[7])};
+  __builtin_nontemporal_store(t, reinterpret_cast<u4v*>(p));
+}
+__device__ __forceinline__ void vstore(uint16_t* p, const float (&v)[1]) {
+  __builtin_nontemporal_store((uint16_t)cvt_pk_bf16(v[0], 0.f), p);
+}
+
+// One row per gather instruction (CPL = 8: up to 512 columns per grid.y
+// block; CPL = 1: NV 64-column blocks, the scalar form).
+template <int CPL, int NV, int U, bool VALS, bool BWD>
+__global__ __launch_bounds__(256) void spmm_bf16io_kernel(
+    int64_t num_rows, int64_t self_rows, int S, int hs, const int32_t* __restrict__ ptr,
+    const int32_t* __restrict__ idx, const int32_t* __restrict__ eidv, const float* __restrict__ vals,
+    uint64_t edge_base, uint64_t self_base, int64_t self_row0, const uint16_t* __restrict__ src, int64_t lds, int F,
+    uint16_t* __restrict__ out, int64_t ldo, int zseg, DropDev de, SplitDev sp) {
+  using bits_t = typename BitsT<CPL>::type;
+  de = resolve_key(de);
+  const int lane = threadIdx.x & 63;
+  const int cbase = blockIdx.y * (64 * CPL * NV);
+  int coff[NV];
+  bool cval[NV];
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    coff[k] = cbase + (k * 64 + lane) * CPL;
+    cval[k] = coff[k] < F;
+  }
+  const int nseg_row = BWD ? 1 : S;
+  const int64_t zstride = (int64_t)(S + hs) * zseg;  // bwd self term: dZ row stride
+  const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + uniform_i(threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  const int64_t num_items = sp.num_chunks + num_rows;
+
+  for (int64_t item = wave0; item < num_items; item += nwaves) {
+    float acc[NV][CPL];
+#pragma unroll
+    for (int k = 0; k < NV; ++k) vzero(acc[k]);
+    int pv, nseg;
+    const bool part = item < sp.num_chunks;  // a chunk of a heavy segment -> fp32 partial row
+    float* pbase = nullptr;
+    uint16_t* obase = nullptr;
+    if (part) {
+      const int64_t c = item;
+      pv = lane == 0 ? sp.chunk_begin[c] : (lane == 1 ? sp.chunk_end[c] : 0);
+      nseg = 1;
+      pbase = sp.partials + c * F;
+    } else {
+      const int64_t n = item - sp.num_chunks;
+      uint16_t* orow = out + n * ldo;
+      pv = lane <= nseg_row ? ptr[n * nseg_row + lane] : 0;
+      nseg = nseg_row;
+      const bool heavy = readlane_i(pv, nseg) - readlane_i(pv, 0) > sp.threshold;
+      // ---- self term: stored (forward), or the head of the column's sum (backward)
+      if (hs && (!BWD || (n < self_rows && !heavy))) {
+        float w = 1.0f;
+        if (de.active && de.drop_self) w = dropedge_weight(de, 1.0f, self_base + (uint64_t)n);
+        const uint16_t* srow = BWD ? src + n * zstride : src + (n + self_row0) * lds;
+#pragma unroll
+        for (int k = 0; k < NV; ++k) {
+          if (cval[k]) {
+            float x[CPL];
+            widen(*reinterpret_cast<const bits_t*>(srow + coff[k]), x);
+            vself(x, w);
+            if (BWD) {
+#pragma unroll
+              for (int i = 0; i < CPL; ++i) acc[k][i] = x[i];
+            } else {
+              vstore(orow + coff[k], x);
+            }
+          }
+        }
+      }
+      if (heavy) continue;  // typed segments / the column come from the chunk partials (fixup)
+      obase = BWD ? orow : orow + hs * zseg;
+    }
+
+    const int e_begin = readlane_i(pv, 0);
+    const int e_end = readlane_i(pv, nseg);
+    int t = 0;
+    int seg_end = readlane_i(pv, 1);
+    for (int c0 = e_begin; c0 < e_end; c0 += 64) {
+      const int cnt = min(64, e_end - c0);
+      int sidx = 0;
+      float w = 0.0f;
+      if (lane < cnt) {
+        sidx = idx[c0 + lane];
+        const float v = VALS ? vals[c0 + lane] : 1.0f;
+        w = v;
+        if (de.active) {  // the CSC edge-id list is only read when DropEdge draws
+          const uint64_t id = BWD ? edge_base + (uint64_t)(uint32_t)eidv[c0 + lane]
+                                  : edge_base + (uint64_t)(c0 + lane);
+          w = dropedge_weight(de, v, id);
+        }
+      }
+      uint64_t kept = __ballot(w != 0.0f);
+      while (kept) {
+        int jj[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (kept) {
+            jj[u] = __builtin_ctzll(kept);
+            kept &= kept - 1;
+          } else {
+            jj[u] = -1;
+          }
+        }
+        bits_t xv[U][NV];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (jj[u] >= 0) {
+            const int r = readlane_i(sidx, jj[u]);
+            const uint16_t* srow = src + (int64_t)r * lds;
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+              if (cval[k])
+                xv[u][k] = *reinterpret_cast<const bits_t*>(srow + coff[k]);
+              else
+                xv[u][k] = bits_t{};
+            }
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          if (jj[u] >= 0) {
+            const int e = c0 + jj[u];
+            while (!BWD && e >= seg_end) {  // flush finished segments (wave-uniform; never inside a chunk)
+#pragma unroll
+              for (int k = 0; k < NV; ++k) {
+                if (cval[k]) vstore(obase + t * zseg + coff[k], acc[k]);
+                vzero(acc[k]);
+              }
+              ++t;
+              seg_end = readlane_i(pv, t + 1);
+            }
+            const float wj = readlane_f(w, jj[u]);
+#pragma unroll
+            for (int k = 0; k < NV; ++k) {
+              float x[CPL];
+              widen(xv[u][k], x);
+              vfma(acc[k], wj, x);
+            }
+          }
+        }
+      }
+    }
+    // ---- the partial row, or the remaining (possibly empty) segments -------
+    if (part) {
+#pragma unroll
+      for (int k = 0; k < NV; ++k)
+        if (cval[k]) vstore(pbase + coff[k], acc[k]);
+      continue;
+    }
+    for (; t < nseg; ++t) {
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        if (cval[k]) vstore(obase + t * zseg + coff[k], acc[k]);
+        vzero(acc[k]);
+      }
+    }
+  }
+}
+
+// Rows of at most 256 columns: two entries per gather instruction, as
+// spmm_bf16_pair_kernel.  GRL_SPMM_BF16IO_PAIR_WAVES: the waves-per-SIMD bound
+// of its A/B.
+#ifndef GRL_SPMM_BF16IO_PAIR_WAVES
+#define GRL_SPMM_BF16IO_PAIR_WAVES 8
+#endif
+template <int U, bool VALS, bool BWD>
+__global__ __launch_bounds__(256, GRL_SPMM_BF16IO_PAIR_WAVES) void spmm_bf16io_pair_kernel(
+    int64_t num_rows, int64_t self_rows, int S, int hs, const int32_t* __restrict__ ptr,
+    const int32_t* __restrict__ idx, const int32_t* __restrict__ eidv, const float* __restrict__ vals,
+    uint64_t edge_base, uint64_t self_base, int64_t self_row0, const uint16_t* __restrict__ src, int64_t lds, int F,
+    uint16_t* __restrict__ out, int64_t ldo, int zseg, DropDev de, SplitDev sp) {
+  de = resolve_key(de);
+  const int nseg_row = BWD ? 1 : S;
+  const int lane = threadIdx.x & 63;
+  const int half = lane >> 5;
+  const int coff = (lane & 31) * 8;
+  const bool ld_ok = coff < F;
+  const bool own = half == 0 && ld_ok;
+  const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + uniform_i(threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  const int64_t num_items = sp.num_chunks + num_rows;
+
+  for (int64_t item = wave0; item < num_items; item += nwaves) {
+    float acc[8];
+    vzero(acc);
+    int pv, nseg;
+    const bool part = item < sp.num_chunks;
+    float* pbase = nullptr;
+    uint16_t* obase = nullptr;
+    if (part) {
+      const int64_t c = item;
+      pv = lane == 0 ? sp.chunk_begin[c] : (lane == 1 ? sp.chunk_end[c] : 0);
+      nseg = 1;
+      pbase = sp.partials + c * F;
+    } else {
+      const int64_t n = item - sp.num_chunks;
+      uint16_t* orow = out + n * ldo;
+      pv = lane <= nseg_row ? ptr[n * nseg_row + lane] : 0;
+      nseg = nseg_row;
+      const bool heavy = readlane_i(pv, nseg) - readlane_i(pv, 0) > sp.threshold;
+      if (hs && (!BWD || (n < self_rows && !heavy))) {
+        float w = 1.0f;
+        if (de.active && de.drop_self) w = dropedge_weight(de, 1.0f, self_base + (uint64_t)n);
+        if (own) {
+          const uint16_t* srow = BWD ? src + n * ((int64_t)(S + hs) * zseg) : src + (n + self_row0) * lds;
+          float x[8];
+          widen(*reinterpret_cast<const uint4*>(srow + coff), x);
+          vself(x, w);
+          if (BWD) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) acc[i] = x[i];
+          } else {
+            vstore(orow + coff, x);
+          }
+        }
+      }
+      if (heavy) continue;
+      obase = BWD ? orow : orow + hs * zseg;
+    }
+
+    const int e_begin = readlane_i(pv, 0);
+    const int e_end = readlane_i(pv, nseg);
+    int t = 0;
+    int seg_end = readlane_i(pv, 1);
+    for (int c0 = e_begin; c0 < e_end; c0 += 64) {
+      const int cnt = min(64, e_end - c0);
+      int sidx = 0;
+      float w = 0.0f;
+      if (lane < cnt) {
+        sidx = idx[c0 + lane];
+        const float v = VALS ? vals[c0 + lane] : 1.0f;
+        w = v;
+        if (de.active) {
+          const uint64_t id = BWD ? edge_base + (uint64_t)(uint32_t)eidv[c0 + lane]
+                                  : edge_base + (uint64_t)(c0 + lane);
+          w = dropedge_weight(de, v, id);
+        }
+      }
+      uint64_t kept = __ballot(w != 0.0f);
+      while (kept) {
+        int jj[2 * U];
+#pragma unroll
+        for (int u = 0; u < 2 * U; ++u) {
+          if (kept) {
+            jj[u] = __builtin_ctzll(kept);
+            kept &= kept - 1;
+          } else {
+            jj[u] = -1;
+          }
+        }
+        uint4 xv[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+          const int ja = jj[2 * u], jb = jj[2 * u + 1];
+          if (ja >= 0) {
+            const int ra = readlane_i(sidx, ja);
+            const int rb = jb >= 0 ? readlane_i(sidx, jb) : ra;
+            const int r = half ? rb : ra;
+            if (ld_ok && (half == 0 || jb >= 0))
+              xv[u] = *reinterpret_cast<const uint4*>(src + (int64_t)r * lds + coff);
+            else
+              xv[u] = uint4{};
+          }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int j = jj[2 * u + h];
+            if (j < 0) continue;
+            const int e = c0 + j;
+            while (!BWD && e >= seg_end) {  // flush finished segments (wave-uniform; never inside a chunk)
+              if (own) vstore(obase + t * zseg + coff, acc);
+              vzero(acc);
+              ++t;
+              seg_end = readlane_i(pv, t + 1);
+            }
+            const float wj = readlane_f(w, j);
+            uint4 b = xv[u];
+            if (h == 1) b = make_uint4(swap_halves(b.x), swap_halves(b.y), swap_halves(b.z), swap_halves(b.w));
+            float x[8];
+            widen(b, x);
+            vfma(acc, wj, x);
+          }
+        }
+      }
+    }
+    if (part) {
+      if (own) vstore(pbase + coff, acc);
+      continue;
+    }
+    for (; t < nseg; ++t) {
+      if (own) vstore(obase + t * zseg + coff, acc);
+      vzero(acc);
+    }
+  }
+}
+
+// Heavy segment (forward) or column (backward) h: [the self term, backward]
+// + its chunk partials in chunk order in fp32, rounded once at the store.
+// One wavefront per heavy segment; VEC = 8: 16 B of bf16 a lane.
+template <int VEC, bool BWD>
+__global__ __launch_bounds__(256) void spmm_bf16io_fixup_kernel(
+    int64_t num_heavy, const int32_t* __restrict__ heavy_seg, const int32_t* __restrict__ heavy_cptr,
+    const float* __restrict__ partials, int nseg, int S, int hs, int64_t self_rows, uint64_t self_base,
+    const uint16_t* __restrict__ dZ, int F, uint16_t* __restrict__ out, int64_t ldo, int zseg, DropDev de) {
+  using bits_t = typename BitsT<VEC>::type;
+  de = resolve_key(de);
+  const int lane = threadIdx.x & 63;
+  const int64_t zstride = (int64_t)(S + hs) * zseg;  // bwd: dZ row stride
+  const int64_t wave0 = (int64_t)blockIdx.x * (blockDim.x >> 6) + uniform_i(threadIdx.x >> 6);
+  const int64_t nwaves = (int64_t)gridDim.x * (blockDim.x >> 6);
+  for (int64_t h = wave0; h < num_heavy; h += nwaves) {
+    const int64_t s = heavy_seg[h];
+    const int64_t n = s / nseg, t = s % nseg;
+    const int c_begin = heavy_cptr[h], c_end = heavy_cptr[h + 1];
+    float w_self = 0.0f;
+    if (BWD && hs && n < self_rows) {
+      w_self = 1.0f;
+      if (de.active && de.drop_self) w_self = dropedge_weight(de, 1.0f, self_base + (uint64_t)n);
+    }
+    uint16_t* orow = BWD ? out + n * ldo : out + n * ldo + (hs + t) * zseg;
+    for (int col = lane * VEC; col < F; col += 64 * VEC) {
+      float acc[VEC];
+      vzero(acc);
+      if (BWD && w_self != 0.0f) {
+        widen(*reinterpret_cast<const bits_t*>(dZ + n * zstride + col), acc);
+        vself(acc, w_self);
+      }
+      for (int c = c_begin; c < c_end; ++c) {
+        const float* p = partials + (int64_t)c * F + col;
+#pragma unroll
+        for (int q = 0; q < VEC / 4; ++q) {
+          const float4 v = reinterpret_cast<const float4*>(p)[q];
+          acc[4 * q] += v.x, acc[4 * q + 1] += v.y, acc[4 * q + 2] += v.z, acc[4 * q + 3] += v.w;
+        }
+        if constexpr (VEC == 1) acc[0] += p[0];
+      }
+      vstore(orow + col, acc);
+    }
+  }
+}
+
 __global__ void mask_kernel(DropDev de, uint64_t id_base, int64_t count, uint8_t* __restrict__ keep) {
   de = resolve_key(de);
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count;
@@ -1061,8 +1423,74 @@ int launch_spmm_fwd(const GrlTypedCsr* g, const float* X, int64_t ldx, int F, in
                             stream, Z, self_row0, -1, zseg);
 }
 
-int launch_spmm_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, int64_t self_row0, float* Z,
-                     int64_t ldz, int zseg, const DropDev& de, hipStream_t stream) {
+// bf16 rows gathered, bf16 rows written: the forward into a bf16 Z (BWD =
+// false: ptr = rowptr, idx = colidx) and the backward over a bf16 dZ (BWD =
+// true: ptr = colptr, idx = zrow, src = dZ + col0 with lds = zseg = F_total).
+// The shapes are launch_spmm_bf16's, with a lane's 8 columns stored as 16 B.
+template <bool BWD>
+int launch_spmm_bf16io(int64_t num_rows, int64_t self_rows, int S, int hs, const int32_t* ptr, const int32_t* idx,
+                       const int32_t* eid, const float* vals, uint64_t edge_base, uint64_t self_base,
+                       int64_t self_row0, const uint16_t* src, int64_t lds, int F, uint16_t* out, int64_t ldo,
+                       int zseg, const DropDev& de, const GrlSplitPlan* plan, hipStream_t stream) {
+  SplitDev sp;
+  const int rc = to_split_dev(plan, F, sp);
+  if (rc) return rc;
+  // 16 B loads of the gathered rows and 16 B stores of the output (the partials are F floats apart)
+  const bool vec = al16(src) && al16(out) && lds % 8 == 0 && F % 8 == 0 && ldo % 8 == 0 && zseg % 8 == 0;
+  const int nv = F <= 64 ? 1 : (F <= 128 ? 2 : 4);
+  const int ycols = vec ? 512 : 64 * nv;
+  const ItemGrid ig = item_grid(num_rows + sp.num_chunks);
+  const dim3 grid(ig.x, (unsigned)ceil_div(F, ycols));
+  const dim3 block(256);
+#define GRL_BF16IO_LAUNCH(...)                                                                                  \
+  hipLaunchKernelGGL((__VA_ARGS__), grid, block, 0, stream, num_rows, self_rows, S, hs, ptr, idx, eid, vals,    \
+                     edge_base, self_base, self_row0, src, lds, F, out, ldo, zseg, de, sp)
+  if (vec && F <= 256) {
+    if (vals) GRL_BF16IO_LAUNCH(spmm_bf16io_pair_kernel<8, true, BWD>); else GRL_BF16IO_LAUNCH(spmm_bf16io_pair_kernel<8, false, BWD>);
+  } else if (vec) {
+    if (vals) GRL_BF16IO_LAUNCH(spmm_bf16io_kernel<8, 1, 8, true, BWD>); else GRL_BF16IO_LAUNCH(spmm_bf16io_kernel<8, 1, 8, false, BWD>);
+  } else if (nv == 1) {
+    if (vals) GRL_BF16IO_LAUNCH(spmm_bf16io_kernel<1, 1, 8, true, BWD>); else GRL_BF16IO_LAUNCH(spmm_bf16io_kernel<1, 1, 8, false, BWD>);
+  } else if (nv == 2) {
+    if (vals) GRL_BF16IO_LAUNCH(spmm_bf16io_kernel<1, 2, 8, true, BWD>); else GRL_BF16IO_LAUNCH(spmm_bf16io_kernel<1, 2, 8, false, BWD>);
+  } else {
+    if (vals) GRL_BF16IO_LAUNCH(spmm_bf16io_kernel<1, 4, 8, true, BWD>); else GRL_BF16IO_LAUNCH(spmm_bf16io_kernel<1, 4, 8, false, BWD>);
+  }
+#undef GRL_BF16IO_LAUNCH
+  GRL_LAUNCH_CHECK();
+  if (plan && plan->num_heavy > 0) {
+    const dim3 fgrid((unsigned)std::min<int64_t>(ceil_div(plan->num_heavy, 4), ig.cap));
+    const int nseg = BWD ? 1 : S;
+    if (vec)
+      hipLaunchKernelGGL((spmm_bf16io_fixup_kernel<8, BWD>), fgrid, block, 0, stream, plan->num_heavy,
+                         plan->heavy_seg, plan->heavy_cptr, plan->partials, nseg, S, hs, self_rows, self_base, src, F,
+                         out, ldo, zseg, de);
+    else
+      hipLaunchKernelGGL((spmm_bf16io_fixup_kernel<1, BWD>), fgrid, block, 0, stream, plan->num_heavy,
+                         plan->heavy_seg, plan->heavy_cptr, plan->partials, nseg, S, hs, self_rows, self_base, src, F,
+                         out, ldo, zseg, de);
+    GRL_LAUNCH_CHECK();
+  }
+  return GRL_OK;
+}
+
+// The forward over a bf16 table into Z of ZT: fp32 (grl_typed_spmm_fwd_bf16)
+// or bf16 bits (grl_typed_spmm_fwd_bf16_to_bf16).
+template <typename ZT>
+int launch_spmm_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, int64_t self_row0, ZT* Z,
+                     int64_t ldz, int zseg, const DropDev& de, hipStream_t stream);
+
+template <>
+int launch_spmm_bf16<uint16_t>(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, int64_t self_row0,
+                               uint16_t* Z, int64_t ldz, int zseg, const DropDev& de, hipStream_t stream) {
+  return launch_spmm_bf16io<false>(g->num_rows, g->num_rows, g->num_types, g->has_self ? 1 : 0, g->rowptr, g->colidx,
+                                   nullptr, g->vals, g->edge_id_base, g->self_id_base, self_row0, X, ldx, F, Z, ldz,
+                                   zseg, de, g->split, stream);
+}
+
+template <>
+int launch_spmm_bf16<float>(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int F, int64_t self_row0, float* Z,
+                            int64_t ldz, int zseg, const DropDev& de, hipStream_t stream) {
   SplitDev sp;
   const int rc = to_split_dev(g->split, F, sp);
   if (rc) return rc;
@@ -1193,13 +1621,15 @@ extern "C" int grl_typed_spmm_fwd(const GrlTypedCsr* g, const float* X, int64_t 
   return launch_spmm_fwd(g, X, ldx, F, g->self_row0, Z, (int64_t)segments(g) * F, F, to_dev(de), as_stream(stream));
 }
 
-// grl_typed_spmm_fwd_slice and grl_typed_spmm_fwd_bf16: the entry `who` over a
-// table of XT, launched by `launch` (launch_spmm_fwd / launch_spmm_bf16).
-template <typename XT>
+// grl_typed_spmm_fwd_slice, grl_typed_spmm_fwd_bf16 and grl_typed_spmm_fwd_bf16_to_bf16: the entry `who` over a
+// table of XT into Z of ZT, launched by `launch` (launch_spmm_fwd / launch_spmm_bf16<ZT>).
+static bool al2(const void* p) { return reinterpret_cast<uintptr_t>(p) % 2 == 0; }
+
+template <typename XT, typename ZT>
 static int spmm_fwd_slice_entry(const char* who, const GrlTypedCsr* g, const XT* X, int64_t ldx, int32_t F,
-                                int64_t self_col0, float* Z, int64_t ldz, int32_t zseg, const GrlDropEdge* de,
+                                int64_t self_col0, ZT* Z, int64_t ldz, int32_t zseg, const GrlDropEdge* de,
                                 grl_stream_t stream,
-                                int (*launch)(const GrlTypedCsr*, const XT*, int64_t, int, int64_t, float*, int64_t,
+                                int (*launch)(const GrlTypedCsr*, const XT*, int64_t, int, int64_t, ZT*, int64_t,
                                               int, const DropDev&, hipStream_t)) {
   TraceRange trace_(who);
   const int rc = csr_fwd_check(who, g, F, ldx, X && Z);
@@ -1208,6 +1638,7 @@ static int spmm_fwd_slice_entry(const char* who, const GrlTypedCsr* g, const XT*
                 (long long)self_col0);
   GRL_CHECK_ARG(ldz >= (int64_t)(segments(g) - 1) * zseg + F, "%s: ldz %lld too small for %d segments of stride %d",
                 who, (long long)ldz, segments(g), zseg);
+  if (sizeof(ZT) == 2) GRL_CHECK_ARG(al2(X) && al2(Z), "%s: X and Z must be 2 B-aligned", who);
   if (g->num_rows == 0) return GRL_OK;
   return launch(g, X, ldx, F, self_col0 + g->self_row0, Z, ldz, zseg, to_dev(de), as_stream(stream));
 }
@@ -1223,13 +1654,23 @@ extern "C" int grl_typed_spmm_fwd_bf16(const GrlTypedCsr* g, const uint16_t* X, 
                                        int64_t self_col0, float* Z, int64_t ldz, int32_t zseg,
                                        const GrlDropEdge* de, grl_stream_t stream) {
   return spmm_fwd_slice_entry("grl_typed_spmm_fwd_bf16", g, X, ldx, F, self_col0, Z, ldz, zseg, de, stream,
-                              launch_spmm_bf16);
+                              launch_spmm_bf16<float>);
+}
+
+extern "C" int grl_typed_spmm_fwd_bf16_to_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx, int32_t F,
+                                               int64_t self_col0, uint16_t* Z, int64_t ldz, int32_t zseg,
+                                               const GrlDropEdge* de, grl_stream_t stream) {
+  return spmm_fwd_slice_entry("grl_typed_spmm_fwd_bf16_to_bf16", g, X, ldx, F, self_col0, Z, ldz, zseg, de, stream,
+                              launch_spmm_bf16<uint16_t>);
 }
 
 // dX columns [0, F) = columns [col0, col0 + F) of A_drop^T dZ, dZ segments
-// F_total wide (F_total = F, col0 = 0: the whole gradient).
-static int spmm_bwd_entry(const char* who, const GrlTypedCsc* g, const float* dZ, int32_t F_total, int32_t col0,
-                          int32_t F, float* dX, int64_t lddx, const GrlDropEdge* de, grl_stream_t stream, bool accum) {
+// F_total wide (F_total = F, col0 = 0: the whole gradient).  T: float (the
+// three fp32 entries), or bf16 bits on both sides (grl_typed_spmm_bwd_bf16,
+// which has no accumulating form).
+template <typename T>
+static int spmm_bwd_entry(const char* who, const GrlTypedCsc* g, const T* dZ, int32_t F_total, int32_t col0,
+                          int32_t F, T* dX, int64_t lddx, const GrlDropEdge* de, grl_stream_t stream, bool accum) {
   GRL_CHECK_ARG(g != nullptr, "%s: graph is NULL", who);
   GRL_CHECK_ARG(g->num_rows >= 0 && g->self_rows >= 0 && g->self_rows <= g->num_rows, "%s: bad num_rows/self_rows",
                 who);
@@ -1243,9 +1684,16 @@ static int spmm_bwd_entry(const char* who, const GrlTypedCsc* g, const float* dZ
   GRL_CHECK_ARG((dZ || (g->nnz == 0 && g->self_rows == 0)) && dX && g->colptr && (g->nnz == 0 || (g->zrow && g->eid)),
                 "%s: NULL pointer", who);
   const int hs = g->has_self ? 1 : 0;
-  return launch_spmm<true>(g->num_rows, g->self_rows, g->num_types, hs, g->colptr, g->zrow, g->eid, g->vals,
-                           g->edge_id_base, g->self_id_base, dZ + col0, (int64_t)F_total, F, dX, lddx, to_dev(de),
-                           g->split, as_stream(stream), dX, 0, -1, F_total, accum);
+  if constexpr (sizeof(T) == 2) {
+    GRL_CHECK_ARG(al2(dZ) && al2(dX), "%s: dZ and dX must be 2 B-aligned", who);
+    return launch_spmm_bf16io<true>(g->num_rows, g->self_rows, g->num_types, hs, g->colptr, g->zrow, g->eid, g->vals,
+                                    g->edge_id_base, g->self_id_base, 0, dZ + col0, (int64_t)F_total, F, dX, lddx,
+                                    F_total, to_dev(de), g->split, as_stream(stream));
+  } else {
+    return launch_spmm<true>(g->num_rows, g->self_rows, g->num_types, hs, g->colptr, g->zrow, g->eid, g->vals,
+                             g->edge_id_base, g->self_id_base, dZ + col0, (int64_t)F_total, F, dX, lddx, to_dev(de),
+                             g->split, as_stream(stream), dX, 0, -1, F_total, accum);
+  }
 }
 
 extern "C" int grl_typed_spmm_bwd_accum(const GrlTypedCsc* g, const float* dZ, int32_t F, float* dX, int64_t lddx,
@@ -1265,6 +1713,13 @@ extern "C" int grl_typed_spmm_bwd_slice(const GrlTypedCsc* g, const float* dZ, i
                                         grl_stream_t stream) {
   TraceRange trace_("grl_typed_spmm_bwd_slice");
   return spmm_bwd_entry("grl_typed_spmm_bwd_slice", g, dZ, F_total, col0, F, dX, lddx, de, stream, false);
+}
+
+extern "C" int grl_typed_spmm_bwd_bf16(const GrlTypedCsc* g, const uint16_t* dZ, int32_t F_total, int32_t col0,
+                                       int32_t F, uint16_t* dX, int64_t lddx, const GrlDropEdge* de,
+                                       grl_stream_t stream) {
+  TraceRange trace_("grl_typed_spmm_bwd_bf16");
+  return spmm_bwd_entry("grl_typed_spmm_bwd_bf16", g, dZ, F_total, col0, F, dX, lddx, de, stream, false);
 }
 
 extern "C" size_t grl_split_plan_workspace_size(int64_t rows) {

@@ -143,6 +143,10 @@ SIGNATURES = {
                                           _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_fwd_bf16": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_i64, _c_vp, _c_i64, _c_i32,
                                          _P(GrlDropEdge), _c_vp]),
+    "grl_typed_spmm_fwd_bf16_to_bf16": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_i64, _c_vp, _c_i64, _c_i32,
+                                                 _P(GrlDropEdge), _c_vp]),
+    "grl_typed_spmm_bwd_bf16": (_c_i32, [_P(GrlTypedCsc), _c_vp, _c_i32, _c_i32, _c_i32, _c_vp, _c_i64,
+                                         _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_bwd": (_c_i32, [_P(GrlTypedCsc), _c_vp, _c_i32, _c_vp, _c_i64, _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_bwd_accum": (_c_i32, [_P(GrlTypedCsc), _c_vp, _c_i32, _c_vp, _c_i64, _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_bwd_slice": (_c_i32, [_P(GrlTypedCsc), _c_vp, _c_i32, _c_i32, _c_i32, _c_vp, _c_i64,

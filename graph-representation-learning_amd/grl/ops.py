@@ -66,7 +66,18 @@ def _graphconv_fwd_call(entry: str, csr, X2, F, Wc, bc, relu: bool, out, Z, grap
          current_stream_handle(X2.device))
 
 
-def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: bool = False):
+def _want_bf16(who: str, out, out_dtype) -> bool:
+    """Whether a call's result is bfloat16: by its `out` tensor, or by
+    `out_dtype` (None: float32) when it makes a new one."""
+    if out_dtype not in (None, torch.float32, torch.bfloat16):
+        raise _lib.GrlError(f"{who}: out_dtype must be torch.float32 or torch.bfloat16 (got {out_dtype})")
+    if out is not None and out_dtype is not None and out.dtype != out_dtype:
+        raise _lib.GrlError(f"{who}: out is {out.dtype}, out_dtype {out_dtype}")
+    return (out.dtype if out is not None else out_dtype) == torch.bfloat16
+
+
+def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: bool = False,
+                  z_dtype=torch.float32):
     """The checked operands of a forward over `graph` -- (X2, F, Wc, bc, out,
     Z): the features' 2-D row view and width, the contiguous weights
     [segments * F, C] and bias (None without), out [num_rows, C] (with
@@ -74,7 +85,9 @@ def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: 
     fp32 tensor given or a new one.  The features may be bfloat16 (the table
     is read as stored); weights and bias are float32.  With bfloat16 features
     `out` may be a bfloat16 [num_rows, C] tensor with unit column stride and
-    any row stride (a column-slice view of a wider table), written in place."""
+    any row stride (a column-slice view of a wider table), written in place.
+    z_dtype = torch.bfloat16 (bfloat16 features only): Z is a contiguous
+    bfloat16 tensor instead."""
     _require_device(X, "node features")
     if X.dtype not in _TABLE_DTYPES:
         raise _lib.GrlError(f"{who}: node features must be float32 or bfloat16 (got {X.dtype})")
@@ -89,10 +102,14 @@ def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: 
     if Wc is not None and Wc.shape[0] != K:
         raise _lib.GrlError(f"weights have {Wc.shape[0]} rows, expected {graph.segments} x {F}")
 
-    def target(t, what, cols):
+    if z_dtype == torch.bfloat16 and X.dtype != torch.bfloat16:
+        raise _lib.GrlError(f"{who}: a bfloat16 Z needs bfloat16 node features (got {X.dtype}): there is no mixed "
+                            "form -- cast the table once")
+
+    def target(t, what, cols, dtype=torch.float32):
         shape = (graph.num_rows, cols)
         if t is None:
-            return torch.empty(shape, dtype=torch.float32, device=X.device)
+            return torch.empty(shape, dtype=dtype, device=X.device)
         if what == "out" and t.dtype == torch.bfloat16:
             if X.dtype != torch.bfloat16:
                 raise _lib.GrlError(f"{who}: a bfloat16 out needs bfloat16 node features (got {X.dtype}): there is no "
@@ -101,25 +118,32 @@ def _forward_args(who: str, X, graph, W=None, b=None, out=None, Z=None, want_Z: 
                 raise _lib.GrlError(f"{who}: a bfloat16 out must be a {shape} tensor on {X.device} with unit column "
                                     "stride and a row stride of at least its width")
             return t
-        if tuple(t.shape) != shape or t.dtype != torch.float32 or not t.is_contiguous() or t.device != X.device:
-            raise _lib.GrlError(f"{who}: {what} must be a contiguous float32 {shape} tensor on {X.device}")
+        if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != X.device:
+            name = "float32" if dtype == torch.float32 else "bfloat16"
+            raise _lib.GrlError(f"{who}: {what} must be a contiguous {name} {shape} tensor on {X.device}")
         return t
 
     return (X2, F, Wc, b.contiguous() if b is not None else None,
-            target(out, "out", Wc.shape[1]) if Wc is not None else None, target(Z, "Z", K) if want_Z else None)
+            target(out, "out", Wc.shape[1]) if Wc is not None else None, target(Z, "Z", K, z_dtype) if want_Z else None)
 
 
-def spmm_forward(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor = None) -> torch.Tensor:
+def spmm_forward(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor = None, out_dtype=None) -> torch.Tensor:
     """Z = A_drop X without autograd bookkeeping, optionally into `out`
-    (contiguous [num_rows, segments*F] fp32): the inference / benchmark form.
+    (contiguous [num_rows, segments*F]): the inference / benchmark form.
     X float32 or bfloat16 (read as stored: half the gather bytes, Z bitwise
-    the fp32 result on X.float())."""
+    the fp32 result on X.float()).  Z is float32 unless `out` is bfloat16 or
+    out_dtype = torch.bfloat16 (bfloat16 X only; there is no mixed form): then
+    Z is that fp32 result rounded once to nearest even, written as bfloat16
+    by the kernel (grl_typed_spmm_fwd_bf16_to_bf16) -- no fp32 Z exists."""
+    z16 = _want_bf16("spmm_forward", out, out_dtype)
     if isinstance(graph, EdgeBlockedGraph):
-        return _blocked_forward(X, graph, out)
-    X2, F, _, _, _, Z = _forward_args("spmm_forward", X, graph, Z=out, want_Z=True)
+        return _blocked_forward(X, graph, out, torch.bfloat16 if z16 else torch.float32)
+    X2, F, _, _, _, Z = _forward_args("spmm_forward", X, graph, Z=out, want_Z=True,
+                                      z_dtype=torch.bfloat16 if z16 else torch.float32)
     if X2.dtype == torch.bfloat16:
-        call("grl_typed_spmm_fwd_bf16", ctypes.byref(graph.csr_c(F)), X2.data_ptr(), X2.stride(0), F, 0, Z.data_ptr(),
-             graph.segments * F, F, _de_ref(graph), current_stream_handle(X.device))
+        call("grl_typed_spmm_fwd_bf16_to_bf16" if z16 else "grl_typed_spmm_fwd_bf16", ctypes.byref(graph.csr_c(F)),
+             X2.data_ptr(), X2.stride(0), F, 0, Z.data_ptr(), graph.segments * F, F, _de_ref(graph),
+             current_stream_handle(X.device))
         return Z
     call("grl_typed_spmm_fwd", ctypes.byref(graph.csr_c(F)), X2.data_ptr(), X2.stride(0), F, Z.data_ptr(),
          _de_ref(graph), current_stream_handle(X.device))
@@ -132,9 +156,10 @@ def spmm_forward_slice(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor, co
     [num_rows, segments * F_total]), where X is that column slice's table
     ([graph.num_cols, F], any row stride) and row n's self term reads X row
     self_col0 + n (grl_typed_spmm_fwd_slice; a bfloat16 table:
-    grl_typed_spmm_fwd_bf16).  Bitwise equal, per element, to the whole-width
-    spmm_forward: the pipelined halo exchange of grl.dist aggregates one slice
-    while the next is in flight."""
+    grl_typed_spmm_fwd_bf16, into a bfloat16 `out`
+    grl_typed_spmm_fwd_bf16_to_bf16).  Bitwise equal, per element, to the
+    whole-width spmm_forward: the pipelined halo exchange of grl.dist
+    aggregates one slice while the next is in flight."""
     _require_device(X, "node features")
     if X.dtype not in _TABLE_DTYPES or X.dim() != 2 or X.stride(1) != 1:
         raise _lib.GrlError("slice table must be a 2-D float32 or bfloat16 tensor with unit column stride")
@@ -142,30 +167,36 @@ def spmm_forward_slice(X: torch.Tensor, graph: TypedGraph, out: torch.Tensor, co
         raise _lib.GrlError(f"slice table has {X.shape[0]} rows, graph gathers from {graph.num_cols}")
     F = X.shape[1]
     S = graph.segments
-    if out.dtype != torch.float32 or not out.is_contiguous() or out.shape[0] != graph.num_rows \
+    if out.dtype not in _TABLE_DTYPES or not out.is_contiguous() or out.shape[0] != graph.num_rows \
             or out.shape[1] % S or out.device != X.device:
-        raise _lib.GrlError(f"out must be a contiguous float32 [{graph.num_rows}, {S} x F_total] tensor")
+        raise _lib.GrlError(f"out must be a contiguous float32 [{graph.num_rows}, {S} x F_total] tensor "
+                            "(bfloat16 for a bfloat16 table)")
+    if out.dtype == torch.bfloat16 and X.dtype != torch.bfloat16:
+        raise _lib.GrlError(f"a bfloat16 out needs a bfloat16 slice table (got {X.dtype}): there is no mixed form")
     zseg = out.shape[1] // S
     if col0 < 0 or col0 + F > zseg:
         raise _lib.GrlError(f"columns [{col0}, {col0 + F}) outside the {zseg}-column segments")
-    entry = "grl_typed_spmm_fwd_bf16" if X.dtype == torch.bfloat16 else "grl_typed_spmm_fwd_slice"
+    entry = "grl_typed_spmm_fwd_slice" if X.dtype == torch.float32 else \
+        "grl_typed_spmm_fwd_bf16" + ("_to_bf16" if out.dtype == torch.bfloat16 else "")
     call(entry, ctypes.byref(graph.csr_c(F)), X.data_ptr(), X.stride(0), F, int(self_col0),
-         out.data_ptr() + 4 * col0, out.stride(0), zseg, _de_ref(graph), current_stream_handle(X.device))
+         out.data_ptr() + out.element_size() * col0, out.stride(0), zseg, _de_ref(graph),
+         current_stream_handle(X.device))
     return out
 
 
-def _blocked_forward(X: torch.Tensor, graph: EdgeBlockedGraph, out: torch.Tensor = None) -> torch.Tensor:
-    """Z of a graph with >= 2^31 edges: one aggregation per row block (self
-    rows at the block's first row, Z rows likewise)."""
+def _blocked_forward(X: torch.Tensor, graph: EdgeBlockedGraph, out: torch.Tensor = None,
+                     dtype=torch.float32) -> torch.Tensor:
+    """Z (of `dtype`) of a graph with >= 2^31 edges: one aggregation per row
+    block (self rows at the block's first row, Z rows likewise)."""
     X2 = _rows_view(X)
     if X2.shape[0] != graph.num_cols:
         raise _lib.GrlError(f"features have {X2.shape[0]} rows, graph gathers from {graph.num_cols}")
     F = X2.shape[1]
     shape = (graph.num_rows, graph.segments * F)
     if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=X.device)
-    elif tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != torch.float32:
-        raise _lib.GrlError(f"out must be a contiguous float32 {shape} tensor")
+        out = torch.empty(shape, dtype=dtype, device=X.device)
+    elif tuple(out.shape) != shape or not out.is_contiguous() or out.dtype != dtype:
+        raise _lib.GrlError(f"out must be a contiguous {dtype} {shape} tensor")
     for blk, r0, r1 in zip(graph.blocks, graph.row_bounds[:-1], graph.row_bounds[1:]):
         spmm_forward_slice(X2, blk, out[r0:r1], 0, self_col0=r0)
     return out
@@ -188,61 +219,109 @@ def _blocked_backward(dZ: torch.Tensor, graph: EdgeBlockedGraph, F: int) -> torc
     return dX
 
 
-def spmm_backward(dZ: torch.Tensor, graph: TypedGraph, F: int) -> torch.Tensor:
-    """dX = A_drop^T dZ (grl_typed_spmm_bwd over the cached CSC, same mask)."""
+def _bwd_out(who: str, out, graph, F, dtype, device):
+    """dX [graph.num_cols, F] of `dtype`: the tensor given (unit column
+    stride, any row stride) or a new one."""
+    if out is None:
+        return torch.empty(graph.num_cols, F, dtype=dtype, device=device)
+    if tuple(out.shape) != (graph.num_cols, F) or out.dtype != dtype or out.stride(1) != 1 or out.stride(0) < F \
+            or out.device != device:
+        raise _lib.GrlError(f"{who}: out must be a {dtype} [{graph.num_cols}, {F}] tensor on {device} with unit "
+                            "column stride")
+    return out
+
+
+def spmm_backward(dZ: torch.Tensor, graph: TypedGraph, F: int, out: torch.Tensor = None,
+                  out_dtype=None) -> torch.Tensor:
+    """dX = A_drop^T dZ (grl_typed_spmm_bwd over the cached CSC, same mask),
+    optionally into `out` ([graph.num_cols, F], unit column stride).  dX is
+    float32 -- a bfloat16 dZ is widened first -- unless `out` is bfloat16 or
+    out_dtype = torch.bfloat16: then dZ must be bfloat16 (there is no mixed
+    form), is gathered as stored (an expanded or transposed gradient is copied
+    once, in bfloat16) and dX is the fp32 result on dZ.float() rounded once to
+    nearest even, written as bfloat16 by the kernel (grl_typed_spmm_bwd_bf16):
+    no widened dZ and no fp32 dX exist.  An EdgeBlockedGraph gives the same
+    bits through its fp32 accumulating chain, rounded at the end."""
+    x16 = _want_bf16("spmm_backward", out, out_dtype)
+    if x16 and dZ.dtype != torch.bfloat16:
+        raise _lib.GrlError(f"spmm_backward: a bfloat16 dX needs a bfloat16 dZ (got {dZ.dtype}): there is no mixed form")
     if isinstance(graph, EdgeBlockedGraph):
-        return _blocked_backward(dZ, graph, F)
+        dX = _blocked_backward(dZ, graph, F)
+        if out is None:
+            return dX.to(torch.bfloat16) if x16 else dX
+        return _bwd_out("spmm_backward", out, graph, F, out.dtype, dZ.device).copy_(dX)
+    if x16:
+        _require_device(dZ, "dZ")
+        dZ = dZ.reshape(graph.num_rows, graph.segments * F)
+        if not dZ.is_contiguous():
+            dZ = dZ.contiguous()
+        dX = _bwd_out("spmm_backward", out, graph, F, torch.bfloat16, dZ.device)
+        call("grl_typed_spmm_bwd_bf16", ctypes.byref(graph.csc_c(F)), dZ.data_ptr(), F, 0, F, dX.data_ptr(),
+             dX.stride(0), _de_ref(graph), current_stream_handle(dZ.device))
+        return dX
     dZ = dZ.contiguous().float()
-    dX = torch.empty(graph.num_cols, F, dtype=torch.float32, device=dZ.device)
-    call("grl_typed_spmm_bwd", ctypes.byref(graph.csc_c(F)), dZ.data_ptr(), F, dX.data_ptr(), F, _de_ref(graph),
-         current_stream_handle(dZ.device))
+    dX = _bwd_out("spmm_backward", out, graph, F, torch.float32, dZ.device)
+    call("grl_typed_spmm_bwd", ctypes.byref(graph.csc_c(F)), dZ.data_ptr(), F, dX.data_ptr(), dX.stride(0),
+         _de_ref(graph), current_stream_handle(dZ.device))
     return dX
 
 
 def spmm_backward_slice(dZ: torch.Tensor, graph: TypedGraph, col0: int, out: torch.Tensor) -> torch.Tensor:
     """Columns [col0, col0 + F) of dX = A_drop^T dZ into `out` ([graph.num_cols,
-    F] float32, unit column stride, any row stride), dZ contiguous
-    [num_rows, segments * F_total] (grl_typed_spmm_bwd_slice).  Bitwise equal,
+    F], unit column stride, any row stride), dZ contiguous
+    [num_rows, segments * F_total] (grl_typed_spmm_bwd_slice).  dZ and out are
+    both float32 or both bfloat16 (grl_typed_spmm_bwd_bf16).  Bitwise equal,
     per element, to spmm_backward: the pipelined backward of grl.dist sends
     one slice's halo-row gradients home while the next slice gathers."""
     if isinstance(graph, EdgeBlockedGraph):
         raise _lib.GrlError("column-slice backward takes a TypedGraph (edge-blocked graphs: spmm_backward)")
     _require_device(dZ, "dZ")
-    if dZ.dtype != torch.float32 or not dZ.is_contiguous() or dZ.dim() != 2 or dZ.shape[0] != graph.num_rows \
+    if dZ.dtype not in _TABLE_DTYPES or not dZ.is_contiguous() or dZ.dim() != 2 or dZ.shape[0] != graph.num_rows \
             or dZ.shape[1] % graph.segments:
-        raise _lib.GrlError(f"dZ must be a contiguous float32 [{graph.num_rows}, {graph.segments} x F_total] tensor")
+        raise _lib.GrlError(f"dZ must be a contiguous float32 [{graph.num_rows}, {graph.segments} x F_total] tensor "
+                            "(or bfloat16, with a bfloat16 out)")
     F_total = dZ.shape[1] // graph.segments
-    if out.dtype != torch.float32 or out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != graph.num_cols \
-            or out.device != dZ.device:
-        raise _lib.GrlError(f"out must be a float32 [{graph.num_cols}, F] tensor with unit column stride")
+    if out.dtype != dZ.dtype:
+        raise _lib.GrlError(f"dZ is {dZ.dtype}, out {out.dtype}: there is no mixed form")
+    if out.dim() != 2 or out.stride(1) != 1 or out.shape[0] != graph.num_cols or out.device != dZ.device:
+        raise _lib.GrlError(f"out must be a {dZ.dtype} [{graph.num_cols}, F] tensor with unit column stride")
     F = out.shape[1]
-    call("grl_typed_spmm_bwd_slice", ctypes.byref(graph.csc_c(F)), dZ.data_ptr(), F_total, int(col0), F,
+    entry = "grl_typed_spmm_bwd_bf16" if dZ.dtype == torch.bfloat16 else "grl_typed_spmm_bwd_slice"
+    call(entry, ctypes.byref(graph.csc_c(F)), dZ.data_ptr(), F_total, int(col0), F,
          out.data_ptr(), out.stride(0), _de_ref(graph), current_stream_handle(dZ.device))
     return out
 
 
 class _TypedAggregate(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, X: torch.Tensor, graph: TypedGraph) -> torch.Tensor:
-        Z = spmm_forward(X, graph)
+    def forward(ctx, X: torch.Tensor, graph: TypedGraph, out_dtype=None) -> torch.Tensor:
+        Z = spmm_forward(X, graph, out_dtype=out_dtype)
         ctx.graph = graph
         ctx.xshape = X.shape
         ctx.xdtype = X.dtype
+        ctx.z16 = Z.dtype == torch.bfloat16
         return Z
 
     @staticmethod
     def backward(ctx, dZ: torch.Tensor):
-        # Z is fp32 whatever X is, so dZ is: one fp32 transpose pass, rounded once for a bf16 X
-        return spmm_backward(dZ, ctx.graph, ctx.xshape[-1]).view(ctx.xshape).to(ctx.xdtype), None
+        if ctx.z16:  # bf16 dZ gathered as stored, bf16 dX as the kernel writes it: no fp32 pass on either side
+            dX = spmm_backward(dZ, ctx.graph, ctx.xshape[-1], out_dtype=torch.bfloat16)
+            return dX.view(ctx.xshape), None, None
+        # an fp32 Z, so dZ is fp32: one fp32 transpose pass, rounded once for a bf16 X
+        return spmm_backward(dZ, ctx.graph, ctx.xshape[-1]).view(ctx.xshape).to(ctx.xdtype), None, None
 
 
-def typed_aggregate(X: torch.Tensor, graph: TypedGraph) -> torch.Tensor:
+def typed_aggregate(X: torch.Tensor, graph: TypedGraph, out_dtype=None) -> torch.Tensor:
     """Z[n, s*F:(s+1)*F]: segment 0 = own row (identity block), segment 1+t =
     sum over type-t neighbours; rows of X = graph.num_cols.  X float32 or
     bfloat16 (unit column stride, any row stride; a column-slice view is read
-    in place); Z is fp32 either way, and a bfloat16 X gets a bfloat16
-    gradient: the fp32 dX rounded to nearest even."""
-    return _TypedAggregate.apply(X, graph)
+    in place); Z is fp32 by default, and a bfloat16 X gets a bfloat16
+    gradient: the fp32 dX rounded to nearest even.  out_dtype =
+    torch.bfloat16 (bfloat16 X only): Z is bfloat16 -- the fp32 Z rounded once
+    -- and its bfloat16 gradient goes through grl_typed_spmm_bwd_bf16; X.grad
+    is the bfloat16 dX that kernel writes (bitwise the default path's on the
+    widened dZ).  Chained aggregations then pass bfloat16 tables both ways."""
+    return _TypedAggregate.apply(X, graph, out_dtype)
 
 
 # Row count from which the backward applies the ReLU mask to g once

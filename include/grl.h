@@ -290,6 +290,24 @@ int grl_typed_spmm_fwd_bf16(const GrlTypedCsr* g, const uint16_t* X, int64_t ldx
                             int64_t ldz, int32_t zseg, const GrlDropEdge* de,
                             grl_stream_t stream);
 
+/* grl_typed_spmm_fwd_bf16 writing Z as bf16 bits: ldz and zseg counted in
+ * bf16 elements, everything else that entry's (arguments, layout, checks).
+ *   Z is BITWISE the round-to-nearest-even bf16 of the fp32 Z that
+ *   grl_typed_spmm_fwd_bf16 writes on the same arguments -- the self segment,
+ *   every typed segment, and heavy rows after the fixup.
+ * The accumulators and a split plan's chunk partials (num_chunks * F floats,
+ * as for the fp32 entries) stay fp32; the one rounding is at the store, for a
+ * heavy segment in the fixup.  16 B loads and 16 B stores (8 columns a lane)
+ * when X and Z are 16 B-aligned and ldx, F, ldz and zseg are multiples of 8;
+ * one element a lane otherwise.  A pointer that is not 2 B-aligned is
+ * GRL_E_INVALID.  The output of one aggregation is the table of the next
+ * (multi-hop propagation) with no cast pass and no fp32 Z in between.       */
+int grl_typed_spmm_fwd_bf16_to_bf16(const GrlTypedCsr* g, const uint16_t* X,
+                                    int64_t ldx, int32_t F, int64_t self_col0,
+                                    uint16_t* Z, int64_t ldz, int32_t zseg,
+                                    const GrlDropEdge* de,
+                                    grl_stream_t stream);
+
 /* dX = A_drop^T dZ.  Replaces autograd's BmmBackward0 for robust_gcn.py:45
  * (grad of V through the aggregation), with the same DropEdge mask as the
  * forward call that used `de`.  dZ: contiguous [*, (has_self+num_types)*F];
@@ -321,6 +339,24 @@ int grl_typed_spmm_bwd_slice(const GrlTypedCsc* g, const float* dZ,
                              int32_t F_total, int32_t col0, int32_t F,
                              float* dX, int64_t lddx, const GrlDropEdge* de,
                              grl_stream_t stream);
+
+/* grl_typed_spmm_bwd_slice over a gradient stored as bf16 bits, writing dX
+ * as bf16 bits: F_total and lddx counted in bf16 elements, arguments and
+ * checks otherwise that entry's (F_total = F, col0 = 0: the whole gradient).
+ *   dX is BITWISE the round-to-nearest-even bf16 of what
+ *   grl_typed_spmm_bwd[_slice] writes on the exactly widened dZ with the same
+ *   graph, DropEdge record and split plan: the self term first, then the
+ *   column's entries in CSC order, one fmaf each, in fp32; rounded once at the
+ *   store (a heavy column: in the fixup, after its fp32 chunk partials).
+ * The gather moves half the bytes and neither a widened dZ nor an fp32 dX
+ * exists.  16 B loads and stores when dZ + col0 and dX are 16 B-aligned and
+ * F_total, F and lddx are multiples of 8; one element a lane otherwise.  A
+ * pointer that is not 2 B-aligned is GRL_E_INVALID.  There is no accumulating
+ * form: a bf16 dX cannot continue a sum without a second rounding.          */
+int grl_typed_spmm_bwd_bf16(const GrlTypedCsc* g, const uint16_t* dZ,
+                            int32_t F_total, int32_t col0, int32_t F,
+                            uint16_t* dX, int64_t lddx, const GrlDropEdge* de,
+                            grl_stream_t stream);
 
 /* out = Z W + bias (optionally ReLU), fp32-accurate on the matrix cores.
  * Replaces torch.matmul(new_V, self.h_weights) + self.bias
