@@ -178,6 +178,8 @@ int device_cu_count();
   X(OPT_DW_BF16G, "dw_bf16g", 1, 0, 1)                                                    \
   /* 1: grl_linear_bwd_weight_bf16zg eligible (dW from a bf16 Z and gradient); 0: never */ \
   X(OPT_DW_BF16Z, "dw_bf16z", 1, 0, 1)                                                    \
+  /* 1: grl_linear_fwd_bf16x eligible (forward GEMM over a bf16 X); 0: never */            \
+  X(OPT_LINEAR_BF16X, "linear_bf16x", 1, 0, 1)                                            \
   /* 1: persistent warp-specialized one-kernel form; 0: phase-alternating */              \
   X(OPT_FG_WS, "fg_ws", 1, 0, 1)                                                          \
   /* -1: whole-row waves for tables > 12 GB; 1 / 0: always / never */                     \

@@ -883,6 +883,133 @@ __global__ __launch_bounds__(512) void gemm_x6_kernel(GemmArgs p, const uint16_t
 }
 
 // ---------------------------------------------------------------------------
+// gemm_x6_kernel for an A stored as bf16 (grl_linear_fwd_bf16x): A16 holds
+// bf16 bits [M, K], rows p.lda elements apart (p.A is unused).  A bf16 value
+// is plane 0 of its own split and its planes 1 and 2 are +0, so the A tile is
+// DMA'd as it lies into ONE LDS plane -- no landing slots, no split VALU, half
+// the A bytes -- and each accumulator block takes x3a_mfma's three products
+// (a b2, a b1, a b0: x6_mfma's order without the products on a zero plane),
+// 24 MFMAs per wave per K16 step for 48.  The tile, the waves' blocks, the K16
+// steps, sw(), tile_of, B's planes and the epilogue are gemm_x6_kernel's, so
+// every output element is accumulated in its order: bitwise that kernel on the
+// widened A (finite inputs; x6.h at x3a_mfma).
+// LDS: two stages x (1 A plane + 3 B planes) x 8 KB = 64 KB.  Per K16 step a
+// tile's A is 256 rows x 32 B = 512 chunks of 16 B, one dma16 per lane, with
+// B's chunk mapping: chunk c = tid is row c >> 1, and the 16-B half at
+// position c & 1 of that row is the source's half (c & 1) ^ ((row >> 3) & 1)
+// (the swizzle on the source address: the LDS image of a DMA is lane-linear).
+// Step t:  vmcnt(0): own A(t), B(t) landed | barrier: everyone's landed, and
+//          every wave's reads of stage (t+1)&1 (tile t-1) are retired |
+//          DMA A(t+1), B(t+1) -> stage (t+1)&1 | MFMAs on stage t&1.
+// Four DMAs per wave per step, all for the next tile, so the count that leaves
+// nothing the coming reads need in flight is 0; the reads come after the
+// barrier that follows the wait (cdna_hip_programming.md, "Read a staged
+// buffer one phase AFTER the wait that retires it").
+// Preconditions (linear_fwd_bf16x_ok): K % 16 == 0, A16 16-B aligned,
+// lda % 8 == 0.
+constexpr int X3A_STAGE = 4 * X6_PLANE;  // the A plane, then B's three
+
+template <int EPI>
+__global__ __launch_bounds__(512) void gemm_x3a_kernel(GemmArgs p, const uint16_t* __restrict__ A16,
+                                                       const uint16_t* __restrict__ Bp, int64_t Np) {
+  __shared__ __attribute__((aligned(16))) uint16_t smem[2 * X3A_STAGE];  // 2 stages x 32 KB
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;
+  const int l32 = lane & 31, h = lane >> 5;
+  int64_t mi, ni, zi;
+  tile_of(p, mi, ni, zi);
+  const int64_t m0 = mi * LB_M, n0 = ni * LB_N;
+  const int64_t K = p.K;
+  const int64_t nk = K / X6_K;
+
+  auto sw = [](int r, int k) { return r * X6_K + ((((k >> 3) ^ (r >> 3)) & 1) << 3) + (k & 7); };
+  // A: chunk tid of 512 per stage: row tid >> 1 (clamped to M - 1), lands at the A plane + 8 tid
+  const int ar = tid >> 1;
+  const uint16_t* a_src =
+      A16 + min<int64_t>(m0 + ar, p.M - 1) * p.lda + (((tid & 1) ^ (ar >> 3)) & 1) * 8;
+  // B: as in gemm_x6_kernel (chunk c = (3 wave + j) * 64 + lane of 1536 per stage)
+  const int64_t plane_stride = Np * K;
+  const uint16_t* b_src[3];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    const int c = (wave * 3 + j) * 64 + lane;
+    const int n = (c & 511) >> 1;
+    b_src[j] = Bp + (c >> 9) * plane_stride + (n0 + n) * K + (((c & 1) ^ (n >> 3)) & 1) * 8;
+  }
+  auto issue = [&](int64_t t, uint16_t* st) {
+    dma16(a_src + t * X6_K, st + wave * 512);
+    uint16_t* bb = st + X6_PLANE + wave * 3 * 512;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) dma16(b_src[j] + t * X6_K, bb + j * 512);
+  };
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+
+  if (nk > 0) issue(0, smem);
+  for (int64_t t = 0; t < nk; ++t) {
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+    __builtin_amdgcn_s_barrier();
+    uint16_t* cur = smem + (int)(t & 1) * X3A_STAGE;
+    if (t + 1 < nk) issue(t + 1, smem + (int)((t + 1) & 1) * X3A_STAGE);
+    bf16x8_t a_[4], b_[2][3];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      a_[i] = *reinterpret_cast<const bf16x8_t*>(cur + sw(wm * 128 + i * 32 + l32, h * 8));
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        b_[j][q] = *reinterpret_cast<const bf16x8_t*>(cur + (1 + q) * X6_PLANE + sw(wn * 64 + j * 32 + l32, h * 8));
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) x3a_mfma(acc[i][j], a_[i], b_[j]);
+  }
+  // gemm_x6_kernel's epilogue (restated: that kernel's text is pinned)
+  float* Cz = p.C;
+  if (m0 + LB_M <= p.M) {  // whole row tile (uniform): row offsets are uniform multiples of ldc
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int64_t gn = n0 + wn * 64 + j * 32 + l32;
+      const float bv = (EPI == EPI_BIAS && p.bias && gn < p.N) ? p.bias[gn] : 0.0f;
+      float* const o = Cz + (m0 + wm * 128 + 4 * h) * p.ldc + gn;
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          float v = acc[i][j][r] + bv;
+          if (EPI == EPI_BIAS && p.relu) v = v > 0.0f ? v : 0.0f;
+          if (gn < p.N) o[(int64_t)(i * 32 + (r & 3) + 8 * (r >> 2)) * p.ldc] = v;
+        }
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int64_t gn = n0 + wn * 64 + j * 32 + l32;
+    if (gn >= p.N) continue;
+    const float bv = (EPI == EPI_BIAS && p.bias) ? p.bias[gn] : 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t gm = m0 + wm * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (gm < p.M) {
+          float v = acc[i][j][r] + bv;
+          if (EPI == EPI_BIAS && p.relu) v = v > 0.0f ? v : 0.0f;
+          Cz[gm * p.ldc + gn] = v;
+        }
+      }
+  }
+}
+
+// ---------------------------------------------------------------------------
 // x6 for the weight gradient dW = Z^T g (grl_linear_bwd_weight at large M):
 // both operands are M/N-contiguous (A(m, k) = Z[k][m], B(k, n) = g[k][n], k =
 // node).  Each K16 step's rows are split into bf16 planes stored as they lie,
@@ -1528,8 +1655,9 @@ int split_b_planes(const float* B, int64_t ldb, int64_t N, int64_t K, uint16_t* 
   return GRL_OK;
 }
 
-// the x6 GEMM on B planes already split into `planes`
-int launch_x6_gemm(GemmArgs a, const uint16_t* planes, hipStream_t st) {
+// the x6 GEMM on B planes already split into `planes`; A16 non-NULL: A is those bf16 bits (rows a.lda
+// apart, a.A unused) on gemm_x3a_kernel -- the same plan, so the same tiles in the same order
+int launch_x6_gemm(GemmArgs a, const uint16_t* planes, hipStream_t st, const uint16_t* A16 = nullptr) {
   const int64_t Np = x6_np(a.N);
   a.mt = ceil_div(a.M, LB_M);
   a.nt = Np / LB_N;
@@ -1538,7 +1666,12 @@ int launch_x6_gemm(GemmArgs a, const uint16_t* planes, hipStream_t st) {
   a.k_per_split = a.K;
   GRL_CHECK_ARG(a.mt * a.nt < 2147483647LL, "gemm: grid too large");
   const dim3 grid((unsigned)(a.mt * a.nt));
-  if (a.bias || a.relu)
+  const bool epi = a.bias || a.relu;
+  if (A16 && epi)
+    hipLaunchKernelGGL(gemm_x3a_kernel<EPI_BIAS>, grid, dim3(512), 0, st, a, A16, planes, Np);
+  else if (A16)
+    hipLaunchKernelGGL(gemm_x3a_kernel<EPI_STORE>, grid, dim3(512), 0, st, a, A16, planes, Np);
+  else if (epi)
     hipLaunchKernelGGL(gemm_x6_kernel<EPI_BIAS>, grid, dim3(512), 0, st, a, planes, Np);
   else
     hipLaunchKernelGGL(gemm_x6_kernel<EPI_STORE>, grid, dim3(512), 0, st, a, planes, Np);
@@ -1574,10 +1707,10 @@ int x6_gemm_rows(const float* A, int64_t rows, int64_t K, const uint16_t* planes
 namespace {
 
 template <bool B_KC>
-int launch_x6(GemmArgs a, void* ws, hipStream_t st) {
+int launch_x6(GemmArgs a, void* ws, hipStream_t st, const uint16_t* A16 = nullptr) {
   uint16_t* planes = static_cast<uint16_t*>(ws);
   const int rc = split_b_planes<B_KC>(a.B, a.ldb, a.N, a.K, planes, st);
-  return rc ? rc : launch_x6_gemm(a, planes, st);
+  return rc ? rc : launch_x6_gemm(a, planes, st, A16);
 }
 
 // The output GEMM on 64-column tiles when that computes less padding (N mod
@@ -1675,6 +1808,51 @@ extern "C" int grl_linear_fwd_ex(const float* Z, int64_t ldz, const float* W, in
   hipStream_t st = as_stream(stream);
   return w_layout ? run_output_gemm<true, true>(a, aligned, "grl_linear_fwd", workspace, workspace_bytes, st)
                   : run_output_gemm<true, false>(a, aligned, "grl_linear_fwd", workspace, workspace_bytes, st);
+}
+
+namespace grl {
+namespace {
+// Whether grl_linear_fwd_bf16x runs the call: the linear_bf16x path option, the x6 path as grl_linear_fwd_ex
+// takes it for these sizes (x6_path_ok with C % 4 == 0, K % 4 == 0 and a 16-B aligned W: that entry's
+// `aligned`), and X's rows on gemm_x3a_kernel's 16-B DMA chunks
+bool linear_fwd_bf16x_ok(const uint16_t* X, int64_t ldx, const float* W, int64_t M, int32_t K, int32_t C,
+                         int64_t path_rows) {
+  return opt(OPT_LINEAR_BF16X) != 0 && x6_path_ok(M, path_rows, C, K) && C % 4 == 0 && K % 4 == 0 && al16(W) &&
+         al16(X) && ldx % 8 == 0;
+}
+}  // namespace
+}  // namespace grl
+
+extern "C" size_t grl_linear_fwd_bf16x_workspace_query(const uint16_t* X, int64_t ldx, const float* W, int64_t M,
+                                                       int32_t K, int32_t C, int64_t path_rows) {
+  if (!X || !W || M <= 0 || K <= 0 || C <= 0 || path_rows < 0 || ldx < K) return 0;
+  return linear_fwd_bf16x_ok(X, ldx, W, M, K, C, path_rows) ? grl_linear_fwd_ex_workspace_size(M, K, C, path_rows) : 0;
+}
+
+extern "C" int grl_linear_fwd_bf16x(const uint16_t* X, int64_t ldx, const float* W, int32_t w_layout,
+                                    const float* bias, float* out, int64_t M, int32_t K, int32_t C, int32_t relu,
+                                    int64_t path_rows, void* workspace, size_t workspace_bytes, grl_stream_t stream) {
+  TraceRange trace_("grl_linear_fwd_bf16x");
+  GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0 && path_rows >= 0, "grl_linear_fwd_bf16x: negative size");
+  GRL_CHECK_ARG(ldx >= K, "grl_linear_fwd_bf16x: ldx (%lld) < K (%d)", (long long)ldx, K);
+  GRL_CHECK_ARG(w_layout == 0 || w_layout == 1, "grl_linear_fwd_bf16x: w_layout must be 0 ([K][C]) or 1 ([C][K])");
+  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(X) % 2 == 0, "grl_linear_fwd_bf16x: a bf16 X must be 2-B aligned");
+  if (M == 0 || C == 0) return GRL_OK;
+  GRL_CHECK_ARG(X && W && out, "grl_linear_fwd_bf16x: NULL pointer");
+  if (!linear_fwd_bf16x_ok(X, ldx, W, M, K, C, path_rows))
+    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_linear_fwd_bf16x: outside the bf16 forward path (M %lld, path_rows %lld, K %d, "
+             "C %d, X's or W's alignment, ldx %% 8, or the linear_bf16x / gemm_x6 options; see "
+             "grl_linear_fwd_bf16x_workspace_query)", (long long)M, (long long)path_rows, K, C);
+  const size_t need = grl_linear_fwd_ex_workspace_size(M, K, C, path_rows);
+  if (!workspace || !al16(workspace) || workspace_bytes < need)
+    GRL_FAIL(GRL_E_WORKSPACE, "grl_linear_fwd_bf16x: workspace %zu < %zu (or not 16-B aligned)", workspace_bytes,
+             need);
+  GemmArgs a = gemm_args(nullptr, ldx, W, w_layout ? K : C, out, C, M, C, K);
+  a.bias = bias;
+  a.relu = relu;
+  a.path_rows = path_rows;
+  hipStream_t st = as_stream(stream);
+  return w_layout ? launch_x6<true>(a, workspace, st, X) : launch_x6<false>(a, workspace, st, X);
 }
 
 extern "C" int grl_linear_fwd(const float* Z, int64_t ldz, const float* W, const float* bias, float* out, int64_t M,

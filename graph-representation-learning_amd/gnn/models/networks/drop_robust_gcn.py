@@ -190,8 +190,12 @@ class GraphCNNDropEdge(BaseNetwork):
     The embedding is cast once; gcn1 writes the table's columns [0, C), gcn2
     gathers from that slice and writes [C, 2C), gcn3 gathers from the whole
     table (no torch.cat, no cast pass: each layer's kernel rounds its fp32
-    result once as it stores it) and returns bfloat16; emb2 takes
-    cat[g1, g3].float(), and everything after it is fp32 as ever.  It applies
+    result once as it stores it) and returns bfloat16; emb2 takes the bfloat16
+    cat[g1, g3] as stored (grl.ops.row_linear: read in place by
+    grl_linear_fwd_bf16x where that entry applies -- from 122,071 nodes at
+    net_size 256 with the linear_bf16x path option on -- and widened inside the
+    node elsewhere, the same bits either way), and everything after it is fp32
+    as ever.  It applies
     in eval mode with gradients disabled (torch.no_grad) on an unsharded
     TypedGraph on the GPU.  In every other situation -- training mode
     (train_activation_dtype below is the switch there), gradients enabled, a
@@ -206,8 +210,9 @@ class GraphCNNDropEdge(BaseNetwork):
     into the layer's autograd node (grl.ops.graph_conv(..., fdrop=)): gcn2
     reads g1, gcn3 reads cat[g1, g2] (torch.cat on bfloat16), and the gradients
     between the layers are bfloat16 -- the one-kernel data gradient gathers
-    them as stored, dW reads them as stored.  emb2 takes cat[g1, g3].float();
-    everything from there on is fp32 as ever, and so are all parameters and
+    them as stored, dW reads them as stored.  emb2 takes the bfloat16
+    cat[g1, g3] as stored (as above; its backward hands back the bfloat16
+    gradient .float() would); everything from there on is fp32 as ever, and so are all parameters and
     their gradients.  The feature masks are those of the fp32 model (the same
     element ids and hash).  Everywhere else -- eval mode, a node-range shard, a
     dense A, the CPU, the default None -- this attribute is ignored and today's
@@ -314,8 +319,8 @@ class GraphCNNDropEdge(BaseNetwork):
 
     def _gcn_bf16(self, V: torch.Tensor, graph: TypedGraph, ds: bool) -> torch.Tensor:
         """emb1 and the three GraphConv layers of an eval forward with their
-        activations in one bfloat16 table (activation_dtype): emb2's fp32
-        input cat[g1, g3]."""
+        activations in one bfloat16 table (activation_dtype): emb2's
+        bfloat16 input cat[g1, g3]."""
         C = self.net_size
         emb = self._embed(V)  # (eval: the feature dropouts are the identity)
         lead = emb.shape[:-1]
@@ -324,13 +329,13 @@ class GraphCNNDropEdge(BaseNetwork):
         g1 = self.gcn1.propagate(x0, self.edge_dropout(graph, ds), relu=True, out=table[:, :C])
         self.gcn2.propagate(g1, self.edge_dropout(graph, ds), relu=True, out=table[:, C:])
         g3 = self.gcn3.propagate(table, self.edge_dropout(graph, ds), relu=True, out_dtype=torch.bfloat16)
-        return torch.cat([g1, g3], dim=-1).float().view(*lead, 2 * C)
+        return torch.cat([g1, g3], dim=-1).view(*lead, 2 * C)
 
     def _gcn_bf16_train(self, V: torch.Tensor, graph: TypedGraph, ds: bool) -> torch.Tensor:
         """emb1 and the three GraphConv layers of a training forward with
         bfloat16 activations (train_activation_dtype): each layer one autograd
         node with its ReLU and feature dropout, the gradients between them
-        bfloat16; emb2's fp32 input cat[g1, g3]."""
+        bfloat16; emb2's bfloat16 input cat[g1, g3]."""
         C = self.net_size
         emb = self._embed(V)
         lead = emb.shape[:-1]
@@ -344,10 +349,11 @@ class GraphCNNDropEdge(BaseNetwork):
                                  z_dtype=zd)
         g3 = self.gcn3.propagate(torch.cat([g1, g2], dim=-1), self.edge_dropout(graph, ds), relu=True,
                                  dropout=self.dropout, out_dtype=bf16, z_dtype=zd)
-        return torch.cat([g1, g3], dim=-1).float().view(*lead, 2 * C)
+        return torch.cat([g1, g3], dim=-1).view(*lead, 2 * C)
 
     def _head(self, x: torch.Tensor, graph, sharded: bool, pr: int) -> torch.Tensor:
-        """emb2 -> attention -> random projection -> classifier over x = cat[g1, g3]."""
+        """emb2 -> attention -> random projection -> classifier over x = cat[g1, g3]
+        (float32, or bfloat16 from the bf16 GraphConv paths: emb2 reads it as stored)."""
         new_v = apply_linear(self.emb2, x, path_rows=pr)
         if self.use_attention:
             new_v = self.self_atten(new_v, shard=graph) if sharded else self.self_atten(new_v)

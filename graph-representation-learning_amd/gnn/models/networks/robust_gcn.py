@@ -53,8 +53,13 @@ def apply_linear(mod: nn.Module, x: torch.Tensor, relu: bool = False, path_rows:
 
 
 def linear_rows(x: torch.Tensor, W: torch.Tensor, b, relu: bool, path_rows: int = 0) -> torch.Tensor:
+    """A bfloat16 x goes to row_linear as stored (read in place where
+    grl_linear_fwd_bf16x applies, widened inside where not: the same bits
+    either way); torch's path takes it widened."""
     if _on_grl(x, path_rows):
-        return row_linear(x.float(), W, b, relu=relu, path_rows=path_rows)
+        return row_linear(x if x.dtype == torch.bfloat16 else x.float(), W, b, relu=relu, path_rows=path_rows)
+    if x.dtype == torch.bfloat16:
+        x = x.float()
     y = torch.nn.functional.linear(x, W, b)
     return torch.relu(y) if relu else y
 

@@ -189,6 +189,9 @@ SIGNATURES = {
     "grl_linear_fwd_path": (_c_i32, [_c_i64, _c_i32, _c_i32, _c_i64]),
     "grl_linear_fwd_ex": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i32, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32, _c_i64,
                                    _c_vp, _c_size, _c_vp]),
+    "grl_linear_fwd_bf16x_workspace_query": (_c_size, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i32, _c_i32, _c_i64]),
+    "grl_linear_fwd_bf16x": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i32, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32,
+                                      _c_i64, _c_vp, _c_size, _c_vp]),
     "grl_linear_bwd_data_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32]),
     "grl_linear_bwd_data": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_vp, _c_size,
                                      _c_vp]),

@@ -1265,11 +1265,48 @@ def linear_fwd_ex(X2: torch.Tensor, W: torch.Tensor, w_layout: int, b, relu: boo
     return out
 
 
+def linear_fwd_bf16x(X16: torch.Tensor, W: torch.Tensor, w_layout: int, b, relu: bool, path_rows: int = 0):
+    """out = X16 W (+ b) [ReLU] with the bfloat16 X read as stored
+    (grl_linear_fwd_bf16x: X DMA'd into one LDS plane of the split-bf16 GEMM,
+    three plane products for six, no widened copy), bitwise
+    linear_fwd_ex(X16.float(), W, w_layout, b, relu, path_rows) -- or None
+    where that entry's workspace query is 0 (below the x6 size floor, X16 off
+    the 16 B grid or its row stride off the 8-element grid, the linear_bf16x or
+    gemm_x6 path option 0, ...); the caller then widens X16.  Nothing is
+    allocated before the query.  X16: 2-D bfloat16 with unit column stride and
+    a row stride of at least its width (a column slice of a wider table is
+    read in place); W float32, [K, C] (w_layout 0) or [C, K] (1), contiguous."""
+    _require_device(X16, "linear_fwd_bf16x X")
+    if not _bf16_rows(X16):
+        raise _lib.GrlError("linear_fwd_bf16x: X must be a 2-D bfloat16 tensor with unit column stride and a row "
+                            "stride of at least its width (an expanded tensor: .contiguous() first)")
+    M, K = X16.shape
+    if (W.dtype != torch.float32 or W.dim() != 2 or not W.is_contiguous() or W.device != X16.device
+            or W.shape[1 if w_layout else 0] != K):
+        raise _lib.GrlError(f"linear_fwd_bf16x: W must be a contiguous float32 [{K}, C] (w_layout 0) or [C, {K}] "
+                            f"(w_layout 1) tensor on {X16.device}")
+    C = W.shape[0] if w_layout else W.shape[1]
+    ws_bytes = _lib.lib().grl_linear_fwd_bf16x_workspace_query(X16.data_ptr(), _ld(X16), W.data_ptr(), M, K, C,
+                                                               int(path_rows))
+    if ws_bytes == 0:
+        return None
+    out = torch.empty(M, C, dtype=torch.float32, device=X16.device)
+    ws = _workspace(ws_bytes, X16.device)
+    call("grl_linear_fwd_bf16x", X16.data_ptr(), _ld(X16), W.data_ptr(), int(w_layout), _ptr(b), out.data_ptr(), M, K,
+         C, int(relu), int(path_rows), _ptr(ws), ws_bytes, current_stream_handle(X16.device))
+    return out
+
+
 class _RowLinear(torch.autograd.Function):
     """nn.Linear (+ ReLU) on the libgrl GEMM: out = X W^T + b.  Every output
     row is the same fp32 operations whatever the row count (both GEMM paths
     are M-invariant and path_rows pins the choice), so a node-range shard's
-    rows are bitwise the one-GPU model's."""
+    rows are bitwise the one-GPU model's.
+    A bfloat16 X2 (W stays float32) is the node of X2.float() followed by this
+    one, bit for bit: where linear_fwd_bf16x applies the forward reads X2 as
+    stored and saves it (no widened copy); elsewhere X2 is widened first.  The
+    backward widens a saved bfloat16 X2 for dW (a transient) and rounds the
+    fp32 dX once to bfloat16, as autograd does through .float()."""
 
     @staticmethod
     def forward(ctx, X2, W, b, relu: bool, path_rows: int):
@@ -1277,7 +1314,12 @@ class _RowLinear(torch.autograd.Function):
         pad = -C % 4  # an output width off the float4 grid (the classifier's 53) runs padded with zero rows of W
         Wc = W.contiguous() if not pad else torch.nn.functional.pad(W, (0, 0, 0, pad))
         bc = None if b is None else (b.contiguous() if not pad else torch.nn.functional.pad(b, (0, pad)))
-        out = linear_fwd_ex(X2, Wc, 1, bc, relu, path_rows)
+        ctx.x16 = X2.dtype == torch.bfloat16
+        out = linear_fwd_bf16x(X2, Wc, 1, bc, relu, path_rows) if ctx.x16 else None
+        if out is None:
+            if ctx.x16:
+                X2 = X2.float()
+            out = linear_fwd_ex(X2, Wc, 1, bc, relu, path_rows)
         ctx.relu, ctx.path_rows, ctx.C = relu, path_rows, C
         ctx.save_for_backward(X2, Wc, out if relu else None)
         return out if not pad else out[:, :C].contiguous()
@@ -1294,8 +1336,12 @@ class _RowLinear(torch.autograd.Function):
         dX = dW = db = None
         if ctx.needs_input_grad[0]:
             dX = linear_fwd_ex(g, W, 0, None, False, ctx.path_rows)  # g [M, C] x W [C, K]
+            if ctx.x16:  # the gradient of X.float(): the fp32 dX rounded once
+                dX = dX.to(torch.bfloat16)
         want_b = ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or want_b:
+            if X2.dtype == torch.bfloat16:  # saved as stored: widened for the fp32 dW entry, freed with this frame
+                X2 = X2.float()
             dWt, db = linear_bwd_weight(X2, g, None, want_b)  # X^T g [K, C]
             dW = dWt.t()[:C] if ctx.needs_input_grad[1] else None
             db = db[:C] if db is not None else None
@@ -1307,12 +1353,17 @@ def row_linear(X: torch.Tensor, W: torch.Tensor, b=None, relu: bool = False, pat
     on the libgrl GEMM (grl_linear_fwd_ex): the row-local linears of
     GraphCNNDropEdge (drop_robust_gcn.py:36-58, robust_gcn.py:81-83).
     path_rows: the row count the GEMM path is chosen for (a node-range
-    shard passes the whole graph's)."""
+    shard passes the whole graph's).  X float32, or bfloat16 read as stored
+    where linear_fwd_bf16x applies (and widened where not): the result and
+    every gradient are bitwise row_linear(X.float(), ...)'s, the gradient of X
+    bfloat16 (_RowLinear)."""
     _require_device(X, "linear input")
-    if X.dtype != torch.float32 or W.dtype != torch.float32:
-        raise _lib.GrlError("row_linear: float32 input and weight required")
+    if X.dtype not in (torch.float32, torch.bfloat16) or W.dtype != torch.float32:
+        raise _lib.GrlError("row_linear: a float32 or bfloat16 input and a float32 weight required")
     lead = X.shape[:-1]
     X2 = _rows_view(X)
+    if X2.dtype == torch.bfloat16 and not _rows_apart(X2):  # an expanded tensor (row stride 0)
+        X2 = X2.contiguous()
     # path_rows >= M: the M-invariant kernels only (never grl_linear_fwd's unpinned large-M tile)
     out = _RowLinear.apply(X2, W, b, relu, int(max(path_rows, X2.shape[0])))
     return out.view(*lead, W.shape[0])

@@ -412,6 +412,35 @@ int grl_linear_fwd_ex(const float* Z, int64_t ldz, const float* W,
 int32_t grl_linear_fwd_path(int64_t M, int32_t K, int32_t C,
                             int64_t path_rows);
 
+/* grl_linear_fwd_ex over an X stored as bf16: X holds bf16
+ * bits [M, K], rows ldx elements apart (a column slice of a wider table is
+ * valid); W, w_layout, bias, out and path_rows as in grl_linear_fwd_ex.  A
+ * bf16 value is plane 0 of its own three-way split, so X is DMA'd as stored
+ * into one LDS plane and each block takes three plane products for six: no
+ * widened copy, half the A bytes, half the MFMAs.
+ * Contract: out is bitwise grl_linear_fwd_ex on the exactly widened X with
+ * the same path_rows and options, for finite inputs (-0 included; NaN and Inf
+ * are outside the contract).
+ * Eligible -- the query answers grl_linear_fwd_ex_workspace_size(M, K, C,
+ * path_rows), the size of W's planes, else 0 -- where grl_linear_fwd_ex would
+ * take its x6 GEMM (grl_linear_fwd_path(M, K, C, path_rows) == 1, C % 4 == 0,
+ * W 16 B-aligned), X is 16 B-aligned with ldx % 8 == 0, and the path option
+ * linear_bf16x is 1.  Anything else: GRL_E_UNSUPPORTED -- there is no second
+ * path inside the library; the caller widens X and runs grl_linear_fwd_ex.
+ * GRL_E_INVALID, decided on the host: a negative size, ldx < K, a w_layout
+ * other than 0 or 1, an odd X address, a NULL X, W or out with M > 0 and
+ * C > 0.  GRL_E_WORKSPACE: a NULL, misaligned or short workspace.  M == 0 or
+ * C == 0: GRL_OK, nothing is written.  Stream-ordered, no host sync.        */
+size_t grl_linear_fwd_bf16x_workspace_query(const uint16_t* X, int64_t ldx,
+                                            const float* W, int64_t M,
+                                            int32_t K, int32_t C,
+                                            int64_t path_rows);
+int grl_linear_fwd_bf16x(const uint16_t* X, int64_t ldx, const float* W,
+                         int32_t w_layout, const float* bias, float* out,
+                         int64_t M, int32_t K, int32_t C, int32_t relu,
+                         int64_t path_rows, void* workspace,
+                         size_t workspace_bytes, grl_stream_t stream);
+
 /* One GraphConv layer forward in one call (inference):
  *   out = relu?( (A_drop X) W + bias )       robust_gcn.py:45-51 (+ the F.relu
  * of drop_robust_gcn.py:76), i.e. grl_typed_spmm_fwd then grl_linear_fwd with
