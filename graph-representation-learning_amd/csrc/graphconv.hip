@@ -547,11 +547,7 @@ __global__ __launch_bounds__(GRL_WS_DIAG_LB) void graphconv_ws_bf16_kernel(
 #define GRL_WS_OUT16_PACK 1
 #endif
 
-// (cvt_pk_bf16, the rounding of the epilogue's stores: grl_internal.h)
-// lane l ^ 1's value (a DPP move within the quad, no LDS)
-__device__ __forceinline__ float swap_lane_pair(float v) {
-  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));  // quad_perm [1, 0, 3, 2]
-}
+// (cvt_pk_bf16, the rounding of the epilogue's stores, and swap_lane_pair, the lane pairs' trade: grl_internal.h)
 
 // The bf16-table forward writing bf16 rows (grl_graphconv_fwd_bf16_to_bf16,
 // _fwd_train_bf16_to_bf16): graphconv_ws_bf16_kernel but for the epilogue's

@@ -147,6 +147,13 @@ __device__ __forceinline__ uint32_t cvt_pk_bf16(float lo, float hi) {
   return r;
 }
 
+// lane l ^ 1's value (a DPP move within the quad, no LDS): the bf16-output epilogues' lane pairs trade one
+// value of each register pair with it and store dwords of two adjacent columns (graphconv_ws_body.inc,
+// gemm_x6_kernel's EPI_BF16)
+__device__ __forceinline__ float swap_lane_pair(float v) {
+  return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, false));  // quad_perm [1, 0, 3, 2]
+}
+
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // roctx range around a C-ABI entry point: `rocprofv3 --marker-trace` shows
@@ -180,6 +187,10 @@ int device_cu_count();
   X(OPT_DW_BF16Z, "dw_bf16z", 1, 0, 1)                                                    \
   /* 1: grl_linear_fwd_bf16x eligible (forward GEMM over a bf16 X); 0: never */            \
   X(OPT_LINEAR_BF16X, "linear_bf16x", 1, 0, 1)                                            \
+  /* 1: grl_linear_bwd_weight_bf16z eligible (dW from a bf16 Z and an fp32 gradient); 0: never */ \
+  X(OPT_DW_BF16Z_F32G, "dw_bf16z_f32g", 1, 0, 1)                                          \
+  /* 1: grl_linear_fwd_to_bf16 eligible (the x6 forward GEMM storing bf16 rows); 0: never */ \
+  X(OPT_LINEAR_OUT_BF16, "linear_out_bf16", 1, 0, 1)                                      \
   /* 1: persistent warp-specialized one-kernel form; 0: phase-alternating */              \
   X(OPT_FG_WS, "fg_ws", 1, 0, 1)                                                          \
   /* -1: whole-row waves for tables > 12 GB; 1 / 0: always / never */                     \

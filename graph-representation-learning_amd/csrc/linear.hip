@@ -43,7 +43,8 @@ namespace {
 
 constexpr int BM = 128, BN = 128;
 
-enum Epilogue { EPI_STORE = 0, EPI_BIAS = 1, EPI_SLAB = 2 };
+// (EPI_BF16: gemm_x6_kernel alone -- bias / ReLU where given, then bf16 rows)
+enum Epilogue { EPI_STORE = 0, EPI_BIAS = 1, EPI_SLAB = 2, EPI_BF16 = 3 };
 
 struct GemmArgs {
   const float* A;
@@ -845,6 +846,45 @@ __global__ __launch_bounds__(512) void gemm_x6_kernel(GemmArgs p, const uint16_t
       stash_a(t + 1, nxt);
     }
   }
+  if constexpr (EPI == EPI_BF16) {
+    // grl_linear_fwd_to_bf16: p.C holds bf16 bits, rows p.ldc bf16 elements apart; each
+    // element is the fp32 epilogue value below (bias and ReLU where given, as EPI_BIAS applies them) rounded
+    // once to nearest even.  The store form of graphconv_ws_body.inc's GRL_WS_OUT16_PACK branch: lanes l and
+    // l ^ 1 (columns n, n + 1; N % 4 == 0, so both or neither are < N) trade one value of each register pair
+    // (2q, 2q + 1: rows m, m + 1); the even lane then stores row m's columns (n, n + 1) as one dword, the odd
+    // lane row m + 1's (n - 1, n): out is 4 B-aligned and ldc even.  The row bound is each lane's own.
+    uint16_t* const out16 = reinterpret_cast<uint16_t*>(p.C);
+    const int odd = lane & 1;
+    auto store_tile = [&](auto whole_c) {
+      constexpr bool WHOLE = decltype(whole_c)::value;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int64_t gn = n0 + wn * 64 + j * 32 + l32;
+        const float bv = (p.bias && gn < p.N) ? p.bias[gn] : 0.0f;
+        const int64_t mr = m0 + wm * 128 + 4 * h + odd;  // this lane's row of register pair 0
+        uint16_t* const o = out16 + mr * p.ldc + (gn - odd);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+          for (int q = 0; q < 8; ++q) {
+            float v0 = acc[i][j][2 * q] + bv, v1 = acc[i][j][2 * q + 1] + bv;
+            if (p.relu) {
+              v0 = v0 > 0.0f ? v0 : 0.0f;
+              v1 = v1 > 0.0f ? v1 : 0.0f;
+            }
+            const float got = swap_lane_pair(odd ? v0 : v1);  // the neighbour column's value of this lane's row
+            const uint32_t pk = odd ? cvt_pk_bf16(got, v1) : cvt_pk_bf16(v0, got);
+            const int row = i * 32 + ((2 * q) & 3) + 8 * (q >> 1);
+            if (gn < p.N && (WHOLE || mr + row < p.M)) *reinterpret_cast<uint32_t*>(o + (int64_t)row * p.ldc) = pk;
+          }
+      }
+    };
+    if (m0 + LB_M <= p.M)  // wave-uniform
+      store_tile(std::true_type{});
+    else
+      store_tile(std::false_type{});
+    return;
+  }
   float* Cz = p.C;
   if (m0 + LB_M <= p.M) {  // whole row tile (uniform): row offsets are uniform multiples of ldc
 #pragma unroll
@@ -1506,6 +1546,188 @@ __global__ __launch_bounds__(512) void gemm_x1t_kernel(GemmArgs p, const uint16_
   }
 }
 
+// ---------------------------------------------------------------------------
+// x3ta: gemm_x6t_kernel for a Z stored as bf16 and an fp32 g
+// (grl_linear_bwd_weight_bf16z) -- the fourth operand
+// combination of the family.  z16(k, m) = bf16 bits at z16[k * p.lda + m]
+// (p.A unused); B is the fp32 g at p.B.  A is staged as gemm_x1t_kernel stages
+// it: one uint2 (4 bf16) a lane per staged row, stored as loaded into ONE
+// plane; B as gemm_x6t_kernel stages it: a float4 a lane per staged row, split
+// into three planes at the stash.  A stage is 1 A plane + 3 B planes (2 x
+// 32 KB); a K16 step costs a wave 4 + 6 fragment reads and 24 MFMAs.
+// Bits: a value stored as bf16 is plane 0 of its own split and its planes 1
+// and 2 are +0 (v - v = +0, for v = -0 too).  Of x6_mfma's six products the
+// three on those planes (a2 b0, a1 b1, a1 b0) add sums of +-0 to an
+// accumulator that starts at +0 and, under round to nearest, is never -0
+// afterwards (x + (+-0) = x for x != 0, +0 + (+-0) = +0); what remains is a0 b2,
+// a0 b1, a0 b0 in x6_mfma's order: x3a_mfma (x6.h; §4.19's argument applied to
+// the other operand, as §4.21 applies it).  Everything else that fixes the
+// order in which a dW element is summed is gemm_x6t_kernel's -- the tile and
+// its waves' blocks, the K16 steps ascending through two LDS stages, the
+// [16 k][256 m] plane layout and its swizzle, the transposed reads, tile_of,
+// the clamped loads, the rows past the split's end loaded clamped and zeroed
+// at the stash, the epilogue and x6t_plan's splits -- so dW is bitwise that
+// kernel's on the exactly widened Z, for finite inputs (-0 included).
+// GRL_X3TA_NR register sets of staged rows (12 VGPRs each): 1, the loads one
+// K16 step ahead of their stash (gemm_x3t_kernel's pipeline); 2 in diagnostic
+// builds (-DGRL_DIAG -DGRL_X3TA_NR=2), gemm_x6t_kernel's deeper form.
+// Preconditions (dw_x6t_ok): z16 8 B-aligned with lda % 4 == 0, g 16 B-aligned
+// with ldb % 4 == 0, M, N multiples of 4.
+#if !defined(GRL_DIAG) || !defined(GRL_X3TA_NR)
+#undef GRL_X3TA_NR
+#define GRL_X3TA_NR 1
+#endif
+constexpr int X3TA_STAGE = 4 * X6_PLANE;  // A's one plane, then B's three
+
+template <int EPI>
+__global__ __launch_bounds__(512) void gemm_x3ta_kernel(GemmArgs p, const uint16_t* __restrict__ z16) {
+  __shared__ __attribute__((aligned(16))) uint16_t smem[2 * X3TA_STAGE];  // 2 stages x (1 A + 3 B) planes x 8 KB
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 2, wn = wave & 3;
+  const int l32 = lane & 31, h = lane >> 5;
+  int64_t mi, ni, zi;
+  tile_of(p, mi, ni, zi);
+  const int64_t m0 = mi * LB_M, n0 = ni * LB_N;
+  const int64_t kbeg = zi * p.k_per_split;
+  const int64_t kend = min(p.K, kbeg + p.k_per_split);
+  const int64_t nk = kend > kbeg ? (kend - kbeg + X6_K - 1) / X6_K : 0;
+
+  // staging: 4-column group f = tid + 512 i of each operand: k row f >> 6, columns (f & 63) * 4 (a uint2 = 4
+  // bf16 of Z, a float4 of g); the staged k rows are wave-uniform, as in gemm_x6t_kernel
+  const int kr0 = __builtin_amdgcn_readfirstlane(tid >> 6), kr1 = kr0 + 8;
+  const int col = (tid & 63) * 4;
+  const int64_t am = min<int64_t>(m0 + col, p.M - 4), bn = min<int64_t>(n0 + col, p.N - 4);
+  const uint16_t* __restrict__ a_base = z16 + am;
+  const float* __restrict__ b_base = p.B + bn;
+  const int st_off0 = kr0 * 256 + (col ^ ((kr0 & 3) << 5));
+  const int st_off1 = kr1 * 256 + (col ^ ((kr1 & 3) << 5));
+  // register sets of staged rows: set j holds step t's rows for t = j (mod NR)
+  constexpr int NR = GRL_X3TA_NR;
+  static_assert(NR == 1 || NR == 2, "the K16 loop is unrolled by two");
+  uint2 ra0[NR], ra1[NR];
+  float4 rb0[NR], rb1[NR];
+  bool in0[NR], in1[NR];  // the staged rows lie inside this split's K range
+  const float4 zero4 = make_float4(0.f, 0.f, 0.f, 0.f);
+  const uint2 zero2 = make_uint2(0u, 0u);
+  // rows past the split's end: loaded clamped (from kbeg), zeroed when stashed (gemm_x6t_kernel's reason)
+#define X3TA_LOAD(t, j)                                                                                   \
+  do {                                                                                                    \
+    const int64_t k_ = kbeg + (t) * X6_K;                                                                 \
+    in0[j] = k_ + kr0 < kend;                                                                             \
+    in1[j] = k_ + kr1 < kend;                                                                             \
+    const int64_t r0_ = in0[j] ? k_ + kr0 : kbeg;                                                         \
+    const int64_t r1_ = in1[j] ? k_ + kr1 : kbeg;                                                         \
+    ra0[j] = *reinterpret_cast<const uint2*>(a_base + r0_ * p.lda);                                       \
+    ra1[j] = *reinterpret_cast<const uint2*>(a_base + r1_ * p.lda);                                       \
+    rb0[j] = *reinterpret_cast<const float4*>(b_base + r0_ * p.ldb);                                      \
+    rb1[j] = *reinterpret_cast<const float4*>(b_base + r1_ * p.ldb);                                      \
+  } while (0)
+#define X3TA_SPLIT(v, base, off)                                                                          \
+  do {                                                                                                    \
+    uint2 q0_, q1_, q2_;                                                                                  \
+    split3(v, q0_, q1_, q2_);                                                                             \
+    *reinterpret_cast<uint2*>((base) + (off)) = q0_;                                                      \
+    *reinterpret_cast<uint2*>((base) + X6_PLANE + (off)) = q1_;                                           \
+    *reinterpret_cast<uint2*>((base) + 2 * X6_PLANE + (off)) = q2_;                                       \
+  } while (0)
+#define X3TA_STASH(st, j)                                                                                 \
+  do {                                                                                                    \
+    if (!in0[j]) ra0[j] = zero2, rb0[j] = zero4; /* wave-uniform: only a split's last K16 step branches */ \
+    if (!in1[j]) ra1[j] = zero2, rb1[j] = zero4;                                                          \
+    *reinterpret_cast<uint2*>((st) + st_off0) = ra0[j];                                                   \
+    *reinterpret_cast<uint2*>((st) + st_off1) = ra1[j];                                                   \
+    X3TA_SPLIT(rb0[j], (st) + X6_PLANE, st_off0);                                                         \
+    X3TA_SPLIT(rb1[j], (st) + X6_PLANE, st_off1);                                                         \
+  } while (0)
+
+  // this lane's transposed-read coordinates: k = 8h + ((lane & 15) >> 2),
+  // column = block base + 16 ((lane >> 4) & 1) + 4 (lane & 3)
+  const int tk = 8 * h + ((lane & 15) >> 2);
+  const int tc = 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
+
+  if (nk > 0) {
+    X3TA_LOAD(0, 0);
+    X3TA_STASH(smem, 0);
+#pragma unroll
+    for (int j = 1; j <= NR; ++j)
+      if (nk > j) X3TA_LOAD(j, j % NR);
+  }
+  __syncthreads();
+  {
+    const lds_u16* s3 = (const lds_u16*)smem;
+    const int sx = (tk & 3) << 5;
+    int oa[4], ob[2];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) oa[i] = tk * 256 + ((wm * 128 + i * 32 + tc) ^ sx);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) ob[j] = tk * 256 + ((wn * 64 + j * 32 + tc) ^ sx);
+    // step t reads LDS stage S = t & 1 and stashes register set J = (t + 1) % NR into the other stage: both
+    // constants of the body (the loop is unrolled by two, and NR is 1 or 2)
+    auto step = [&](int64_t t, auto stage, auto rset) {
+      constexpr int S = decltype(stage)::value;
+      constexpr int J = decltype(rset)::value;
+      const lds_u16* cur = s3 + S * X3TA_STAGE;
+      auto frag = [](const lds_u16* p0) { return tr8s(p0, p0 + 4 * 256); };  // (second block row: 4 k rows on)
+      bf16x8_t a_[4], b_[2][3];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a_[i] = frag(cur + oa[i]);
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int q = 0; q < 3; ++q) b_[j][q] = frag(cur + (1 + q) * X6_PLANE + ob[j]);
+#pragma unroll
+      for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) x3a_mfma(acc[i][j], a_[i], b_[j]);
+      if (t + 1 < nk) {
+        X3TA_STASH(smem + (S ^ 1) * X3TA_STAGE, J);  // the other stage: last read in step t-1
+        if (t + 1 + NR < nk) X3TA_LOAD(t + 1 + NR, J);
+      }
+      __syncthreads();
+    };
+    using I0 = std::integral_constant<int, 0>;
+    using I1 = std::integral_constant<int, 1>;
+    int64_t t = 0;
+    if constexpr (NR == 1) {
+      for (; t + 1 < nk; t += 2) {
+        step(t, I0{}, I0{});
+        step(t + 1, I1{}, I0{});
+      }
+      if (t < nk) step(t, I0{}, I0{});
+    } else {  // NR == 2: the register set to stash is (t + 1) & 1 = the other LDS stage's parity
+      for (; t + 1 < nk; t += 2) {
+        step(t, I0{}, I1{});
+        step(t + 1, I1{}, I0{});
+      }
+      if (t < nk) step(t, I0{}, I1{});
+    }
+  }
+#undef X3TA_LOAD
+#undef X3TA_SPLIT
+#undef X3TA_STASH
+  float* Cz = p.C + (EPI == EPI_SLAB ? zi * p.M * p.ldc : 0);
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int64_t gn = n0 + wn * 64 + j * 32 + l32;
+    if (gn >= p.N) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const int64_t gm = m0 + wm * 128 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+        if (gm < p.M) Cz[gm * p.ldc + gn] = acc[i][j][r];
+      }
+  }
+}
+
 constexpr int GEMM_BK = 32;
 
 template <bool A_KC, bool B_KC, int EPI, int TBN = BN>
@@ -1656,8 +1878,10 @@ int split_b_planes(const float* B, int64_t ldb, int64_t N, int64_t K, uint16_t* 
 }
 
 // the x6 GEMM on B planes already split into `planes`; A16 non-NULL: A is those bf16 bits (rows a.lda
-// apart, a.A unused) on gemm_x3a_kernel -- the same plan, so the same tiles in the same order
-int launch_x6_gemm(GemmArgs a, const uint16_t* planes, hipStream_t st, const uint16_t* A16 = nullptr) {
+// apart, a.A unused) on gemm_x3a_kernel -- the same plan, so the same tiles in the same order.  out_bf16
+// (fp32 A only): a.C holds bf16 bits, rows a.ldc bf16 elements apart, written by gemm_x6_kernel<EPI_BF16>
+int launch_x6_gemm(GemmArgs a, const uint16_t* planes, hipStream_t st, const uint16_t* A16 = nullptr,
+                   bool out_bf16 = false) {
   const int64_t Np = x6_np(a.N);
   a.mt = ceil_div(a.M, LB_M);
   a.nt = Np / LB_N;
@@ -1667,7 +1891,9 @@ int launch_x6_gemm(GemmArgs a, const uint16_t* planes, hipStream_t st, const uin
   GRL_CHECK_ARG(a.mt * a.nt < 2147483647LL, "gemm: grid too large");
   const dim3 grid((unsigned)(a.mt * a.nt));
   const bool epi = a.bias || a.relu;
-  if (A16 && epi)
+  if (out_bf16)
+    hipLaunchKernelGGL(gemm_x6_kernel<EPI_BF16>, grid, dim3(512), 0, st, a, planes, Np);
+  else if (A16 && epi)
     hipLaunchKernelGGL(gemm_x3a_kernel<EPI_BIAS>, grid, dim3(512), 0, st, a, A16, planes, Np);
   else if (A16)
     hipLaunchKernelGGL(gemm_x3a_kernel<EPI_STORE>, grid, dim3(512), 0, st, a, A16, planes, Np);
@@ -1707,10 +1933,10 @@ int x6_gemm_rows(const float* A, int64_t rows, int64_t K, const uint16_t* planes
 namespace {
 
 template <bool B_KC>
-int launch_x6(GemmArgs a, void* ws, hipStream_t st, const uint16_t* A16 = nullptr) {
+int launch_x6(GemmArgs a, void* ws, hipStream_t st, const uint16_t* A16 = nullptr, bool out_bf16 = false) {
   uint16_t* planes = static_cast<uint16_t*>(ws);
   const int rc = split_b_planes<B_KC>(a.B, a.ldb, a.N, a.K, planes, st);
-  return rc ? rc : launch_x6_gemm(a, planes, st, A16);
+  return rc ? rc : launch_x6_gemm(a, planes, st, A16, out_bf16);
 }
 
 // The output GEMM on 64-column tiles when that computes less padding (N mod
@@ -1853,6 +2079,58 @@ extern "C" int grl_linear_fwd_bf16x(const uint16_t* X, int64_t ldx, const float*
   a.path_rows = path_rows;
   hipStream_t st = as_stream(stream);
   return w_layout ? launch_x6<true>(a, workspace, st, X) : launch_x6<false>(a, workspace, st, X);
+}
+
+namespace grl {
+namespace {
+// Whether grl_linear_fwd_to_bf16 runs the call: the linear_out_bf16 path option, the x6 path as grl_linear_fwd_ex
+// takes it for these sizes and operands (x6_path_ok and that entry's `aligned`), and out's rows on the
+// epilogue's dword stores of two columns
+bool linear_fwd_to_bf16_ok(const float* Z, int64_t ldz, const float* W, const uint16_t* out, int64_t ldo, int64_t M,
+                           int32_t K, int32_t C, int64_t path_rows) {
+  return opt(OPT_LINEAR_OUT_BF16) != 0 && x6_path_ok(M, path_rows, C, K) && C % 4 == 0 && K % 4 == 0 && al16(Z) &&
+         al16(W) && ldz % 4 == 0 && reinterpret_cast<uintptr_t>(out) % 4 == 0 && ldo % 2 == 0 && ldo >= C;
+}
+}  // namespace
+}  // namespace grl
+
+extern "C" size_t grl_linear_fwd_to_bf16_workspace_query(const float* Z, int64_t ldz, const float* W,
+                                                         const uint16_t* out, int64_t ldo, int64_t M, int32_t K,
+                                                         int32_t C, int64_t path_rows) {
+  if (!Z || !W || !out || M <= 0 || K <= 0 || C <= 0 || path_rows < 0 || ldz < K || ldo < C) return 0;
+  return linear_fwd_to_bf16_ok(Z, ldz, W, out, ldo, M, K, C, path_rows)
+             ? grl_linear_fwd_ex_workspace_size(M, K, C, path_rows)
+             : 0;
+}
+
+extern "C" int grl_linear_fwd_to_bf16(const float* Z, int64_t ldz, const float* W, int32_t w_layout, const float* bias,
+                                      uint16_t* out, int64_t ldo, int64_t M, int32_t K, int32_t C, int32_t relu,
+                                      int64_t path_rows, void* workspace, size_t workspace_bytes,
+                                      grl_stream_t stream) {
+  TraceRange trace_("grl_linear_fwd_to_bf16");
+  GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0 && path_rows >= 0, "grl_linear_fwd_to_bf16: negative size");
+  GRL_CHECK_ARG(ldz >= K, "grl_linear_fwd_to_bf16: ldz (%lld) < K (%d)", (long long)ldz, K);
+  GRL_CHECK_ARG(ldo >= C, "grl_linear_fwd_to_bf16: ldo (%lld) < C (%d)", (long long)ldo, C);
+  GRL_CHECK_ARG(w_layout == 0 || w_layout == 1, "grl_linear_fwd_to_bf16: w_layout must be 0 ([K][C]) or 1 ([C][K])");
+  GRL_CHECK_ARG(reinterpret_cast<uintptr_t>(out) % 2 == 0, "grl_linear_fwd_to_bf16: a bf16 out must be 2-B aligned");
+  if (M == 0 || C == 0) return GRL_OK;
+  GRL_CHECK_ARG(Z && W && out, "grl_linear_fwd_to_bf16: NULL pointer");
+  if (!linear_fwd_to_bf16_ok(Z, ldz, W, out, ldo, M, K, C, path_rows))
+    GRL_FAIL(GRL_E_UNSUPPORTED, "grl_linear_fwd_to_bf16: outside the bf16-output forward path (M %lld, path_rows "
+             "%lld, K %d, C %d, Z's or W's alignment, ldz %% 4, out off the 4-B grid, an odd ldo, or the "
+             "linear_out_bf16 / gemm_x6 options; see grl_linear_fwd_to_bf16_workspace_query)", (long long)M,
+             (long long)path_rows, K, C);
+  const size_t need = grl_linear_fwd_ex_workspace_size(M, K, C, path_rows);
+  if (!workspace || !al16(workspace) || workspace_bytes < need)
+    GRL_FAIL(GRL_E_WORKSPACE, "grl_linear_fwd_to_bf16: workspace %zu < %zu (or not 16-B aligned)", workspace_bytes,
+             need);
+  // out travels in the fp32 arguments' place: gemm_x6_kernel<EPI_BF16> reads a.C as bf16 bits, a.ldc in bf16 elements
+  GemmArgs a = gemm_args(Z, ldz, W, w_layout ? K : C, reinterpret_cast<float*>(out), ldo, M, C, K);
+  a.bias = bias;
+  a.relu = relu;
+  a.path_rows = path_rows;
+  hipStream_t st = as_stream(stream);
+  return w_layout ? launch_x6<true>(a, workspace, st, nullptr, true) : launch_x6<false>(a, workspace, st, nullptr, true);
 }
 
 extern "C" int grl_linear_fwd(const float* Z, int64_t ldz, const float* W, const float* bias, float* out, int64_t M,
@@ -2035,17 +2313,26 @@ bool dw_rows_aligned(const void* p, bool is16, int64_t ld) {
   return reinterpret_cast<uintptr_t>(p) % (is16 ? 8 : 16) == 0 && ld % 4 == 0;
 }
 
+// the path option of an operand combination, by name and by value (the fp32 entry has none of its own)
+const char* dw_option_name(const DwOperands& o) {
+  return o.z16 ? (o.g16 ? "dw_bf16z" : "dw_bf16z_f32g") : "dw_bf16g";
+}
+bool dw_option(const DwOperands& o) {
+  if (o.z16) return opt(o.g16 ? OPT_DW_BF16Z : OPT_DW_BF16Z_F32G) != 0;
+  return !o.g16 || opt(OPT_DW_BF16G) != 0;
+}
+
 // Whether the x6t family runs the call (gemm_x6t_kernel for fp32 operands,
-// gemm_x3t_kernel for a bf16 g, gemm_x1t_kernel for a bf16 Z and g): the
-// entry's path option (dw_bf16z / dw_bf16g; gemm_x6 is in the shape rule),
-// gemm_x6t_kernel's shape rule, each operand's alignment, and no mask
+// gemm_x3t_kernel for a bf16 g, gemm_x3ta_kernel for a bf16 Z, gemm_x1t_kernel
+// for a bf16 Z and g): the combination's path option (dw_bf16g / dw_bf16z_f32g /
+// dw_bf16z; gemm_x6 is in the shape rule), gemm_x6t_kernel's shape rule, each
+// operand's alignment, and no mask
 bool dw_x6t_ok(const DwOperands& o, int64_t M, int64_t K, int64_t C) {
-  const bool option = o.z16 ? opt(OPT_DW_BF16Z) != 0 : !o.g16 || opt(OPT_DW_BF16G) != 0;
-  return option && !o.relu_out && x6t_shape_ok(M, K, C) && dw_rows_aligned(o.Z, o.z16, o.ldz) &&
+  return dw_option(o) && !o.relu_out && x6t_shape_ok(M, K, C) && dw_rows_aligned(o.Z, o.z16, o.ldz) &&
          dw_rows_aligned(o.g, o.g16, o.ldg);
 }
 
-// The x6t family's launch plan, one for its three kernels: the same splits,
+// The x6t family's launch plan, one for its four kernels: the same splits,
 // tile order and slab reduce, which is what makes dW of the bf16 entries the
 // fp32 entry's on widened operands, bit for bit.  a is the transposed problem
 // (a.M = K rows of dW, a.N = C, a.K = M nodes); returns the slabs used.
@@ -2077,9 +2364,9 @@ int dw_colsum(const DwOperands& o, int64_t M, int32_t C, float* part, float* db,
   return GRL_OK;
 }
 
-// grl_linear_bwd_weight, _bf16g and _bf16zg: one host path.  Outside the x6t
-// family the fp32 entry falls back to the fp32-MFMA kernel; the bf16 entries
-// have no other kernel and answer GRL_E_UNSUPPORTED.
+// grl_linear_bwd_weight, _bf16g, _bf16z and _bf16zg: one host path.  Outside
+// the x6t family the fp32 entry falls back to the fp32-MFMA kernel; the entries
+// with a bf16 operand have no other kernel and answer GRL_E_UNSUPPORTED.
 int linear_bwd_weight_run(const char* who, const DwOperands& o, float* dW, float* db, int64_t M, int32_t K, int32_t C,
                           void* workspace, size_t workspace_bytes, grl_stream_t stream) {
   GRL_CHECK_ARG(M >= 0 && K >= 0 && C >= 0, "%s: negative size", who);
@@ -2099,10 +2386,9 @@ int linear_bwd_weight_run(const char* who, const DwOperands& o, float* dW, float
   }
   GRL_CHECK_ARG(o.Z && o.g && dW, "%s: NULL pointer", who);
   const bool x6t = dw_x6t_ok(o, M, K, C);
-  if (!x6t && o.g16)
+  if (!x6t && (o.z16 || o.g16))
     GRL_FAIL(GRL_E_UNSUPPORTED, "%s: outside the bf16 dW path (M %lld, K %d, C %d, the operands' alignment or the "
-             "%s / gemm_x6 options; see %s_workspace_query)", who, (long long)M, K, C,
-             o.z16 ? "dw_bf16z" : "dw_bf16g", who);
+             "%s / gemm_x6 options; see %s_workspace_query)", who, (long long)M, K, C, dw_option_name(o), who);
   const size_t need = grl_linear_bwd_weight_workspace_size(M, K, C);
   if (!workspace || workspace_bytes < need)
     GRL_FAIL(GRL_E_WORKSPACE, "%s: workspace %zu < %zu", who, workspace_bytes, need);
@@ -2119,11 +2405,16 @@ int linear_bwd_weight_run(const char* who, const DwOperands& o, float* dW, float
     used = x6t_plan(a, slab, dW);
     GRL_CHECK_ARG(a.mt * a.nt * a.zt < 2147483647LL, "gemm: grid too large");
     const dim3 grid((unsigned)(a.mt * a.nt * a.zt)), block(512);
-    if (o.z16) {
+    if (o.z16 && o.g16) {
       if (used > 1)
         hipLaunchKernelGGL(gemm_x1t_kernel<EPI_SLAB>, grid, block, 0, st, a, o.zb(), o.gb());
       else
         hipLaunchKernelGGL(gemm_x1t_kernel<EPI_STORE>, grid, block, 0, st, a, o.zb(), o.gb());
+    } else if (o.z16) {
+      if (used > 1)
+        hipLaunchKernelGGL(gemm_x3ta_kernel<EPI_SLAB>, grid, block, 0, st, a, o.zb());
+      else
+        hipLaunchKernelGGL(gemm_x3ta_kernel<EPI_STORE>, grid, block, 0, st, a, o.zb());
     } else if (o.g16) {
       if (used > 1)
         hipLaunchKernelGGL(gemm_x3t_kernel<EPI_SLAB>, grid, block, 0, st, a, o.gb());
@@ -2182,6 +2473,19 @@ extern "C" int grl_linear_bwd_weight_bf16g(const float* Z, int64_t ldz, const ui
   grl::TraceRange trace_("grl_linear_bwd_weight_bf16g");
   return grl::linear_bwd_weight_run("grl_linear_bwd_weight_bf16g", {Z, false, ldz, g, true, ldg, nullptr}, dW, db, M,
                                     K, C, workspace, workspace_bytes, stream);
+}
+
+extern "C" size_t grl_linear_bwd_weight_bf16z_workspace_query(const uint16_t* Z, int64_t ldz, const float* g, int64_t M,
+                                                              int32_t K, int32_t C) {
+  return grl::dw_bf16_workspace_query({Z, true, ldz, g, false, C, nullptr}, M, K, C);
+}
+
+extern "C" int grl_linear_bwd_weight_bf16z(const uint16_t* Z, int64_t ldz, const float* g, float* dW, float* db,
+                                           int64_t M, int32_t K, int32_t C, void* workspace, size_t workspace_bytes,
+                                           grl_stream_t stream) {
+  grl::TraceRange trace_("grl_linear_bwd_weight_bf16z");
+  return grl::linear_bwd_weight_run("grl_linear_bwd_weight_bf16z", {Z, true, ldz, g, false, C, nullptr}, dW, db, M, K,
+                                    C, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t grl_linear_bwd_weight_bf16zg_workspace_query(const uint16_t* Z, int64_t ldz, const uint16_t* g,

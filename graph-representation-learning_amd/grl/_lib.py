@@ -192,6 +192,10 @@ SIGNATURES = {
     "grl_linear_fwd_bf16x_workspace_query": (_c_size, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i32, _c_i32, _c_i64]),
     "grl_linear_fwd_bf16x": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i32, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_i32,
                                       _c_i64, _c_vp, _c_size, _c_vp]),
+    "grl_linear_fwd_to_bf16_workspace_query": (_c_size, [_c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32,
+                                                         _c_i64]),
+    "grl_linear_fwd_to_bf16": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i32, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32,
+                                        _c_i32, _c_i64, _c_vp, _c_size, _c_vp]),
     "grl_linear_bwd_data_workspace_size": (_c_size, [_c_i64, _c_i32, _c_i32]),
     "grl_linear_bwd_data": (_c_i32, [_c_vp, _c_vp, _c_vp, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_vp, _c_size,
                                      _c_vp]),
@@ -207,6 +211,9 @@ SIGNATURES = {
     "grl_linear_bwd_weight_bf16g_workspace_query": (_c_size, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32]),
     "grl_linear_bwd_weight_bf16g": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32,
                                              _c_vp, _c_size, _c_vp]),
+    "grl_linear_bwd_weight_bf16z_workspace_query": (_c_size, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i32, _c_i32]),
+    "grl_linear_bwd_weight_bf16z": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32, _c_vp,
+                                             _c_size, _c_vp]),
     "grl_linear_bwd_weight_bf16zg_workspace_query": (_c_size, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i32]),
     "grl_linear_bwd_weight_bf16zg": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_vp, _c_i64, _c_i32, _c_i32,
                                               _c_vp, _c_size, _c_vp]),

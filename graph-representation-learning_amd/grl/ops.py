@@ -451,16 +451,18 @@ def linear_bwd_weight(Z2: torch.Tensor, g: torch.Tensor, relu_out, want_db: bool
 
 def _linear_bwd_weight_bf16_run(entry: str, Z: torch.Tensor, g16: torch.Tensor, want_db: bool):
     """The checked operands through a bf16 dW entry: its workspace query (0: None,
-    before anything is allocated), dW, db and the workspace, the call."""
+    before anything is allocated), dW, db and the workspace, the call.  A
+    float32 g (grl_linear_bwd_weight_bf16z) is dense: that entry takes no ldg."""
     M, K = Z.shape
     C = g16.shape[1]
-    ws_bytes = getattr(_lib.lib(), entry + "_workspace_query")(Z.data_ptr(), _ld(Z), g16.data_ptr(), _ld(g16), M, K, C)
+    g_args = (g16.data_ptr(), _ld(g16)) if g16.dtype == torch.bfloat16 else (g16.data_ptr(),)
+    ws_bytes = getattr(_lib.lib(), entry + "_workspace_query")(Z.data_ptr(), _ld(Z), *g_args, M, K, C)
     if ws_bytes == 0:
         return None
     dW = torch.empty(K, C, dtype=torch.float32, device=g16.device)
     db = torch.empty(C, dtype=torch.float32, device=g16.device) if want_db else None
     ws = _workspace(ws_bytes, g16.device)
-    call(entry, Z.data_ptr(), _ld(Z), g16.data_ptr(), _ld(g16), dW.data_ptr(), _ptr(db), M, K, C, _ptr(ws), ws_bytes,
+    call(entry, Z.data_ptr(), _ld(Z), *g_args, dW.data_ptr(), _ptr(db), M, K, C, _ptr(ws), ws_bytes,
          current_stream_handle(g16.device))
     return dW, db
 
@@ -509,6 +511,27 @@ def linear_bwd_weight_bf16z(Z16: torch.Tensor, g16: torch.Tensor, want_db: bool)
     if Z16.shape[0] != g16.shape[0]:
         raise _lib.GrlError(f"linear_bwd_weight_bf16z: Z has {Z16.shape[0]} rows, g {g16.shape[0]}")
     return _linear_bwd_weight_bf16_run("grl_linear_bwd_weight_bf16zg", Z16, g16, want_db)
+
+
+def linear_bwd_weight_bf16z_f32g(X16: torch.Tensor, g: torch.Tensor, want_db: bool):
+    """(dW, db) = (X16^T g, column sums of g) with the bfloat16 X16 read as
+    stored and g float32 (grl_linear_bwd_weight_bf16z: X16 staged as one plane
+    of the split-bf16 dW GEMM, three plane products for six, no widened copy),
+    bitwise linear_bwd_weight(X16.float(), g, None, want_db) -- or None where
+    that entry's workspace query is 0 (below the x6 size floor, X16 off the 8 B
+    grid, g off the 16 B grid, the dw_bf16z_f32g or gemm_x6 path option 0,
+    ...); the caller then widens X16.  Nothing is allocated before the query.
+    X16 [M, K]: 2-D bfloat16 with unit column stride and a row stride of at
+    least its width (a column slice of a wider table is read in place); g
+    [M, C]: float32, contiguous, already through the ReLU's mask."""
+    _require_device(g, "linear_bwd_weight_bf16z_f32g g")
+    if not _bf16_rows(X16) or X16.device != g.device:
+        raise _lib.GrlError(f"linear_bwd_weight_bf16z_f32g: X must be a 2-D bfloat16 tensor on {g.device} with unit "
+                            "column stride and a row stride of at least its width (an expanded tensor: "
+                            ".contiguous() first)")
+    if g.dtype != torch.float32 or g.dim() != 2 or g.shape[0] != X16.shape[0] or not g.is_contiguous():
+        raise _lib.GrlError(f"linear_bwd_weight_bf16z_f32g: g must be a contiguous float32 [{X16.shape[0]}, C] tensor")
+    return _linear_bwd_weight_bf16_run("grl_linear_bwd_weight_bf16z", X16, g, want_db)
 
 
 class _GraphLinear(torch.autograd.Function):
@@ -1297,6 +1320,47 @@ def linear_fwd_bf16x(X16: torch.Tensor, W: torch.Tensor, w_layout: int, b, relu:
     return out
 
 
+def linear_fwd_to_bf16(X2: torch.Tensor, W: torch.Tensor, w_layout: int, b, relu: bool, path_rows: int = 0,
+                       out: torch.Tensor = None):
+    """out = X2 W (+ b) [ReLU] stored as bfloat16 rows by the GEMM's epilogue
+    (grl_linear_fwd_to_bf16: each fp32 value rounded once to nearest even, no
+    fp32 [M, C] table, no cast pass), bitwise linear_fwd_ex(X2, W, w_layout, b,
+    relu, path_rows).to(torch.bfloat16) -- or None where that entry's workspace
+    query is 0 (off grl_linear_fwd_ex's x6 path, out off the 4 B grid or with an
+    odd row stride, the linear_out_bf16 or gemm_x6 path option 0, ...); the
+    caller then runs linear_fwd_ex and casts.  Nothing is allocated before the
+    query.  X2: 2-D float32 with unit column stride; W
+    float32, [K, C] (w_layout 0) or [C, K] (1), contiguous; out: a bfloat16
+    [M, C] tensor with unit column stride and a row stride of at least C (a
+    column slice of a wider bfloat16 table is written in place), made if None."""
+    _require_device(X2, "linear_fwd_to_bf16 X")
+    if (X2.dtype != torch.float32 or X2.dim() != 2 or (X2.shape[1] > 0 and X2.stride(1) != 1)
+            or not _rows_apart(X2)):
+        raise _lib.GrlError("linear_fwd_to_bf16: X must be a 2-D float32 tensor with unit column stride and a row "
+                            "stride of at least its width")
+    M, K = X2.shape
+    if (W.dtype != torch.float32 or W.dim() != 2 or not W.is_contiguous() or W.device != X2.device
+            or W.shape[1 if w_layout else 0] != K):
+        raise _lib.GrlError(f"linear_fwd_to_bf16: W must be a contiguous float32 [{K}, C] (w_layout 0) or [C, {K}] "
+                            f"(w_layout 1) tensor on {X2.device}")
+    C = W.shape[0] if w_layout else W.shape[1]
+    if out is not None and (not _bf16_rows(out) or out.shape != (M, C) or out.device != X2.device):
+        raise _lib.GrlError(f"linear_fwd_to_bf16: out must be a bfloat16 [{M}, {C}] tensor on {X2.device} with unit "
+                            "column stride and a row stride of at least its width")
+    # (an out still to be made is asked about as what it will be: rows C apart on an allocation's 256 B grid)
+    out_ptr, ldo = (out.data_ptr(), _ld(out)) if out is not None else (256, C)
+    ws_bytes = _lib.lib().grl_linear_fwd_to_bf16_workspace_query(X2.data_ptr(), _ld(X2), W.data_ptr(), out_ptr, ldo,
+                                                                 M, K, C, int(path_rows))
+    if ws_bytes == 0:
+        return None
+    if out is None:
+        out = torch.empty(M, C, dtype=torch.bfloat16, device=X2.device)
+    ws = _workspace(ws_bytes, X2.device)
+    call("grl_linear_fwd_to_bf16", X2.data_ptr(), _ld(X2), W.data_ptr(), int(w_layout), _ptr(b), out.data_ptr(),
+         _ld(out), M, K, C, int(relu), int(path_rows), _ptr(ws), ws_bytes, current_stream_handle(X2.device))
+    return out
+
+
 class _RowLinear(torch.autograd.Function):
     """nn.Linear (+ ReLU) on the libgrl GEMM: out = X W^T + b.  Every output
     row is the same fp32 operations whatever the row count (both GEMM paths
@@ -1305,8 +1369,13 @@ class _RowLinear(torch.autograd.Function):
     A bfloat16 X2 (W stays float32) is the node of X2.float() followed by this
     one, bit for bit: where linear_fwd_bf16x applies the forward reads X2 as
     stored and saves it (no widened copy); elsewhere X2 is widened first.  The
-    backward widens a saved bfloat16 X2 for dW (a transient) and rounds the
-    fp32 dX once to bfloat16, as autograd does through .float()."""
+    backward of a saved bfloat16 X2 reads it as stored for dW
+    (linear_bwd_weight_bf16z_f32g) and has the data-gradient GEMM store the
+    bfloat16 dX itself (linear_fwd_to_bf16: the fp32 dX rounded once, as
+    autograd does through .float()): no fp32 [M, K] table in either direction.
+    Where one of the two returns None (below the x6 floor, its path option 0)
+    that half runs the widened way -- X2.float() for dW, the fp32 GEMM and a
+    cast for dX -- with the same bits."""
 
     @staticmethod
     def forward(ctx, X2, W, b, relu: bool, path_rows: int):
@@ -1334,15 +1403,19 @@ class _RowLinear(torch.autograd.Function):
         if ctx.relu:
             g = torch.where(out > 0, g, torch.zeros((), dtype=g.dtype, device=g.device))
         dX = dW = db = None
-        if ctx.needs_input_grad[0]:
-            dX = linear_fwd_ex(g, W, 0, None, False, ctx.path_rows)  # g [M, C] x W [C, K]
-            if ctx.x16:  # the gradient of X.float(): the fp32 dX rounded once
-                dX = dX.to(torch.bfloat16)
+        if ctx.needs_input_grad[0]:  # g [M, C] x W [C, K]
+            if ctx.x16:  # the gradient of X.float(): the fp32 dX rounded once, by the GEMM's epilogue where it applies
+                dX = linear_fwd_to_bf16(g, W, 0, None, False, ctx.path_rows)
+            if dX is None:
+                dX = linear_fwd_ex(g, W, 0, None, False, ctx.path_rows)
+                if ctx.x16:
+                    dX = dX.to(torch.bfloat16)
         want_b = ctx.needs_input_grad[2]
         if ctx.needs_input_grad[1] or want_b:
-            if X2.dtype == torch.bfloat16:  # saved as stored: widened for the fp32 dW entry, freed with this frame
-                X2 = X2.float()
-            dWt, db = linear_bwd_weight(X2, g, None, want_b)  # X^T g [K, C]
+            # X^T g [K, C]; an X2 saved as bfloat16 is read as stored where that entry applies, else widened for the
+            # fp32 dW entry (a transient, freed with this frame)
+            res = linear_bwd_weight_bf16z_f32g(X2, g, want_b) if X2.dtype == torch.bfloat16 else None
+            dWt, db = res if res is not None else linear_bwd_weight(X2.float(), g, None, want_b)
             dW = dWt.t()[:C] if ctx.needs_input_grad[1] else None
             db = db[:C] if db is not None else None
         return dX, dW, db, None, None
@@ -1356,7 +1429,10 @@ def row_linear(X: torch.Tensor, W: torch.Tensor, b=None, relu: bool = False, pat
     shard passes the whole graph's).  X float32, or bfloat16 read as stored
     where linear_fwd_bf16x applies (and widened where not): the result and
     every gradient are bitwise row_linear(X.float(), ...)'s, the gradient of X
-    bfloat16 (_RowLinear)."""
+    bfloat16 (_RowLinear).  The backward of a bfloat16 X reads it as stored for
+    dW and has the GEMM store the bfloat16 dX where
+    linear_bwd_weight_bf16z_f32g and linear_fwd_to_bf16 apply: no fp32 copy of
+    X or of its gradient."""
     _require_device(X, "linear input")
     if X.dtype not in (torch.float32, torch.bfloat16) or W.dtype != torch.float32:
         raise _lib.GrlError("row_linear: a float32 or bfloat16 input and a float32 weight required")

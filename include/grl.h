@@ -441,6 +441,35 @@ int grl_linear_fwd_bf16x(const uint16_t* X, int64_t ldx, const float* W,
                          int64_t path_rows, void* workspace,
                          size_t workspace_bytes, grl_stream_t stream);
 
+/* grl_linear_fwd_ex writing bf16 rows: Z, W, w_layout, bias,
+ * relu and path_rows as in grl_linear_fwd_ex; out holds bf16 bits [M, C], rows
+ * ldo >= C bf16 elements apart (a column slice of a wider bf16 table is a
+ * valid out).  The x6 GEMM's epilogue rounds each fp32 value once to nearest
+ * even and stores it: no fp32 [M, C] table and no cast pass (the data
+ * gradient of grl_linear_fwd_bf16x's node: g [M, C'] x W [C', K'] -> bf16 dX).
+ * Contract: out is bitwise grl_linear_fwd_ex's fp32 output with the same
+ * path_rows and options rounded to nearest even, for finite values.
+ * Eligible -- the query answers grl_linear_fwd_ex_workspace_size(M, K, C,
+ * path_rows), the size of W's planes, else 0 -- where grl_linear_fwd_ex takes
+ * its x6 GEMM (grl_linear_fwd_path(M, K, C, path_rows) == 1, C % 4 == 0, Z and
+ * W 16 B-aligned, ldz % 4 == 0), out is 4 B-aligned with ldo even, and the path
+ * option linear_out_bf16 is 1.  Anything else: GRL_E_UNSUPPORTED -- there is
+ * no second path inside the library; the caller runs grl_linear_fwd_ex and
+ * casts.  GRL_E_INVALID, decided on the host: a negative size, ldz < K,
+ * ldo < C, a w_layout other than 0 or 1, an odd out address, a NULL Z, W or
+ * out with M > 0 and C > 0.  GRL_E_WORKSPACE: a NULL, misaligned or short
+ * workspace.  M == 0 or C == 0: GRL_OK, nothing is written.  Stream-ordered,
+ * no host sync.                                                             */
+size_t grl_linear_fwd_to_bf16_workspace_query(const float* Z, int64_t ldz,
+                                              const float* W, const uint16_t* out,
+                                              int64_t ldo, int64_t M, int32_t K,
+                                              int32_t C, int64_t path_rows);
+int grl_linear_fwd_to_bf16(const float* Z, int64_t ldz, const float* W,
+                           int32_t w_layout, const float* bias, uint16_t* out,
+                           int64_t ldo, int64_t M, int32_t K, int32_t C,
+                           int32_t relu, int64_t path_rows, void* workspace,
+                           size_t workspace_bytes, grl_stream_t stream);
+
 /* One GraphConv layer forward in one call (inference):
  *   out = relu?( (A_drop X) W + bias )       robust_gcn.py:45-51 (+ the F.relu
  * of drop_robust_gcn.py:76), i.e. grl_typed_spmm_fwd then grl_linear_fwd with
@@ -763,6 +792,36 @@ int grl_linear_bwd_weight_bf16zg(const uint16_t* Z, int64_t ldz, const uint16_t*
                                  int64_t ldg, float* dW, float* db, int64_t M,
                                  int32_t K, int32_t C, void* workspace,
                                  size_t workspace_bytes, grl_stream_t stream);
+
+/* grl_linear_bwd_weight for a Z stored as bf16 and an fp32 g (DESIGN.md
+ * §4.25; the backward of grl_linear_fwd_bf16x's node): Z holds bf16 bits
+ * [M, K], rows ldz >= K elements apart (a column slice of a wider table is a
+ * valid Z), read as stored -- no widened copy; g fp32 [M, C] contiguous:
+ *   dW = Z^T g   [K, C] contiguous        db = sum over rows of g   [C] or NULL
+ * A bf16 value is ONE plane of the split-bf16 scheme, so the kernel
+ * (gemm_x3ta_kernel) stages Z as one plane and issues three plane products per
+ * block where grl_linear_bwd_weight's issues six, three of them on planes that
+ * are all zeros; the other three run in the same order over the same K16
+ * steps, splits and slab order, and db is that entry's.  dW and db are bitwise
+ * grl_linear_bwd_weight(widened Z, g, NULL) for finite operands (-0 included;
+ * NaN and Inf are outside the contract).
+ * Eligible -- the query answers grl_linear_bwd_weight_workspace_size(M, K, C),
+ * else 0 -- where grl_linear_bwd_weight would take its split-bf16 kernel
+ * (gemm_x6 on, M >= 16, K % 4 == 0, C % 4 == 0, 2 M K C >= 1.6e10), Z is 8 B-
+ * aligned with ldz % 4 == 0, g is 16 B-aligned, and the path option
+ * dw_bf16z_f32g is 1.  Anything else: GRL_E_UNSUPPORTED -- there is no second
+ * path inside the library; the caller widens Z and runs grl_linear_bwd_weight.
+ * GRL_E_INVALID, decided on the host: a negative size, ldz < K, an odd Z
+ * address, a NULL Z, g or dW with M > 0.  A missing or short workspace:
+ * GRL_E_WORKSPACE.  M == 0 writes dW = 0 and db = 0; K == 0 or C == 0 returns
+ * GRL_OK.  Stream-ordered, no host sync.                                    */
+size_t grl_linear_bwd_weight_bf16z_workspace_query(const uint16_t* Z, int64_t ldz,
+                                                   const float* g, int64_t M,
+                                                   int32_t K, int32_t C);
+int grl_linear_bwd_weight_bf16z(const uint16_t* Z, int64_t ldz, const float* g,
+                                float* dW, float* db, int64_t M, int32_t K,
+                                int32_t C, void* workspace,
+                                size_t workspace_bytes, grl_stream_t stream);
 
 /* ReLU's derivative applied once (autograd ThresholdBackward of the ReLU at
  * drop_robust_gcn.py:76, the bias gradient of robust_gcn.py:51 with it):

@@ -9,7 +9,8 @@ names normalised away) and hashes them.  tests/test_codegen_pin.py compares
 the hashes with tests/golden/codegen_pins.json: a mismatch means "re-measure
 the kernel on the GPU and re-pin" (python tools/pin_codegen.py --write).
 KERNELS_DW_BF16G is a second pin set with a file and a test of its own
-(tests/golden/codegen_pins_dw_bf16g.json, tests/test_codegen_pin_dw_bf16g.py).
+(tests/golden/codegen_pins_dw_bf16g.json, tests/test_codegen_pin_dw_bf16g.py);
+KERNELS_Z16 and KERNELS_DW_BF16Z_F32G likewise.
 
 --all [--root TREE] hashes every kernel of every source in the Makefile's SRCS
 instead, each file with its own flags (the per-object HIPFLAGS additions
@@ -64,6 +65,14 @@ KERNELS_Z16 = [
      "the same at F=512, C<=256 (gcn3 at d=256)"),
     ("linear.hip", "_ZN3grl12_GLOBAL__N_115gemm_x1t_kernelILi2EEE",
      "dW from a bf16 Z and a bf16 gradient, split-K slabs (grl_linear_bwd_weight_bf16zg at C3)"),
+]
+
+# dW from a bf16 Z and an fp32 gradient (tests/test_codegen_pin_dw_bf16z_f32g.py; profiles/row_linear_bwd_bf16_c3.json)
+PINS_DW_BF16Z_F32G = os.path.join(ROOT, "tests", "golden", "codegen_pins_dw_bf16z_f32g.json")
+KERNELS_DW_BF16Z_F32G = [
+    ("linear.hip", "_ZN3grl12_GLOBAL__N_116gemm_x3ta_kernelILi2EEE",
+     "dW from a bf16 Z and an fp32 gradient, split-K slabs (grl_linear_bwd_weight_bf16z at emb2's shape and C3: "
+     "profiles/row_linear_bwd_bf16_c3.json)"),
 ]
 
 
@@ -144,7 +153,8 @@ if __name__ == "__main__":
         root = sys.argv[sys.argv.index("--root") + 1] if "--root" in sys.argv else ROOT
         print(json.dumps(compute_all(os.path.abspath(root)), indent=1, sort_keys=True))
         sys.exit(0)
-    for path, kernels in ((PINS, KERNELS), (PINS_DW_BF16G, KERNELS_DW_BF16G), (PINS_Z16, KERNELS_Z16)):
+    for path, kernels in ((PINS, KERNELS), (PINS_DW_BF16G, KERNELS_DW_BF16G), (PINS_Z16, KERNELS_Z16),
+                          (PINS_DW_BF16Z_F32G, KERNELS_DW_BF16Z_F32G)):
         pins = compute(kernels)
         if "--write" in sys.argv:
             with open(path, "w") as f:
