@@ -36,6 +36,7 @@ _c_i64 = ctypes.c_int64
 _c_u64 = ctypes.c_uint64
 _c_vp = ctypes.c_void_p
 _c_size = ctypes.c_size_t
+_c_f32 = ctypes.c_float
 
 
 class GrlSplitPlan(ctypes.Structure):
@@ -138,6 +139,13 @@ SIGNATURES = {
     "grl_feature_dropout": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i64, _P(GrlDropEdge), _c_vp]),
     "grl_feature_dropout_bf16": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_i64, _P(GrlDropEdge),
                                           _c_vp]),
+    "grl_bn_rows_workspace_size": (_c_size, [_c_i64, _c_i32]),
+    "grl_bn_rows_fwd_train": (_c_i32, [_c_vp, _c_i64, _c_i64, _c_i32, _c_vp, _c_vp, _c_f32, _c_f32, _c_f32, _c_vp,
+                                       _c_vp, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_size, _c_vp]),
+    "grl_bn_rows_fwd_eval": (_c_i32, [_c_vp, _c_i64, _c_i64, _c_i32, _c_vp, _c_vp, _c_vp, _c_vp, _c_f32, _c_f32,
+                                      _c_vp, _c_i64, _c_vp]),
+    "grl_bn_rows_bwd": (_c_i32, [_c_vp, _c_i64, _c_vp, _c_i64, _c_vp, _c_i64, _c_i64, _c_i32, _c_vp, _c_vp, _c_vp,
+                                 _c_f32, _c_vp, _c_i64, _c_vp, _c_vp, _c_vp, _c_size, _c_vp]),
     "grl_typed_spmm_fwd": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_vp, _P(GrlDropEdge), _c_vp]),
     "grl_typed_spmm_fwd_slice": (_c_i32, [_P(GrlTypedCsr), _c_vp, _c_i64, _c_i32, _c_i64, _c_vp, _c_i64, _c_i32,
                                           _P(GrlDropEdge), _c_vp]),

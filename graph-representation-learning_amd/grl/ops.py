@@ -1271,6 +1271,138 @@ def feature_dropout(x: torch.Tensor, de, row0: int = 0) -> torch.Tensor:
     return _FeatureDropout.apply(x2, de, int(row0)).view(*lead, x.shape[-1])
 
 
+# ------------------------------------------- batch norm over rows + LeakyReLU
+def _bn_rows_table(t: torch.Tensor, what: str, like: torch.Tensor = None) -> None:
+    if (t.dtype != torch.float32 or t.dim() != 2 or (t.shape[1] > 0 and t.stride(1) != 1) or not _rows_apart(t)
+            or (like is not None and (t.shape != like.shape or t.device != like.device))):
+        raise _lib.GrlError(f"batchnorm_rows: {what} must be a 2-D float32 tensor with unit column stride and a row "
+                            f"stride of at least its width (got {t.dtype}, {tuple(t.shape)}, strides {t.stride()})")
+
+
+def _bn_rows_vector(t, what: str, cols: int, device) -> None:
+    if t is not None and (t.dtype != torch.float32 or t.shape != (cols,) or not t.is_contiguous()
+                          or t.device != device):
+        raise _lib.GrlError(f"batchnorm_rows: {what} must be a contiguous float32 [{cols}] tensor on {device}")
+
+
+def batchnorm_rows_fwd_train(x2, weight, bias, running_mean, running_var, momentum, eps, slope, out=None):
+    """(y, save_mean, save_invstd) of grl_bn_rows_fwd_train on a 2-D fp32 row
+    view x2 (a column slice of a wider table included); the running buffers
+    (None: none) are updated in place."""
+    _require_device(x2, "batchnorm_rows input")
+    _bn_rows_table(x2, "x")
+    rows, cols = x2.shape
+    for t, what in ((weight, "weight"), (bias, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _bn_rows_vector(t, what, cols, x2.device)
+    y = torch.empty(rows, cols, dtype=torch.float32, device=x2.device) if out is None else out
+    _bn_rows_table(y, "out", x2)
+    mean = torch.empty(cols, dtype=torch.float32, device=x2.device)
+    invstd = torch.empty(cols, dtype=torch.float32, device=x2.device)
+    ws_bytes = _lib.lib().grl_bn_rows_workspace_size(rows, cols)
+    ws = _workspace(ws_bytes, x2.device)
+    call("grl_bn_rows_fwd_train", x2.data_ptr(), _ld(x2), rows, cols, _ptr(weight), _ptr(bias), float(eps),
+         float(slope), float(momentum), _ptr(running_mean), _ptr(running_var), y.data_ptr(), _ld(y), mean.data_ptr(),
+         invstd.data_ptr(), _ptr(ws), ws_bytes, current_stream_handle(x2.device))
+    return y, mean, invstd
+
+
+def batchnorm_rows_fwd_eval(x2, weight, bias, running_mean, running_var, eps, slope, out=None):
+    """y of grl_bn_rows_fwd_eval on a 2-D fp32 row view; out may be x2 itself
+    (the pass runs in place)."""
+    _require_device(x2, "batchnorm_rows input")
+    _bn_rows_table(x2, "x")
+    rows, cols = x2.shape
+    if running_mean is None or running_var is None:
+        raise _lib.GrlError("batchnorm_rows: the inference form needs running_mean and running_var")
+    for t, what in ((weight, "weight"), (bias, "bias"), (running_mean, "running_mean"), (running_var, "running_var")):
+        _bn_rows_vector(t, what, cols, x2.device)
+    y = torch.empty(rows, cols, dtype=torch.float32, device=x2.device) if out is None else out
+    _bn_rows_table(y, "out", x2)
+    call("grl_bn_rows_fwd_eval", x2.data_ptr(), _ld(x2), rows, cols, _ptr(weight), _ptr(bias), running_mean.data_ptr(),
+         running_var.data_ptr(), float(eps), float(slope), y.data_ptr(), _ld(y), current_stream_handle(x2.device))
+    return y
+
+
+def batchnorm_rows_bwd(dy2, y2, x2, weight, mean, invstd, slope, want_weight=True, want_bias=True, out=None):
+    """(dx, dweight, dbias) of grl_bn_rows_bwd; out may be dy2 itself."""
+    _require_device(dy2, "batchnorm_rows gradient")
+    _bn_rows_table(x2, "x")
+    _bn_rows_table(y2, "y", x2)
+    _bn_rows_table(dy2, "the output gradient", x2)
+    rows, cols = x2.shape
+    dx = torch.empty(rows, cols, dtype=torch.float32, device=x2.device) if out is None else out
+    _bn_rows_table(dx, "out", x2)
+    dw = torch.empty(cols, dtype=torch.float32, device=x2.device) if want_weight else None
+    db = torch.empty(cols, dtype=torch.float32, device=x2.device) if want_bias else None
+    ws_bytes = _lib.lib().grl_bn_rows_workspace_size(rows, cols)
+    ws = _workspace(ws_bytes, x2.device)
+    call("grl_bn_rows_bwd", dy2.data_ptr(), _ld(dy2), y2.data_ptr(), _ld(y2), x2.data_ptr(), _ld(x2), rows, cols,
+         _ptr(weight), mean.data_ptr(), invstd.data_ptr(), float(slope), dx.data_ptr(), _ld(dx), _ptr(dw), _ptr(db),
+         _ptr(ws), ws_bytes, current_stream_handle(x2.device))
+    return dx, dw, db
+
+
+class _BatchNormRows(torch.autograd.Function):
+    """Training-mode batch norm over rows + LeakyReLU as one node: saves x, y,
+    save_mean, save_invstd; the backward is one grl_bn_rows_bwd call."""
+
+    @staticmethod
+    def forward(ctx, x2, weight, bias, running_mean, running_var, momentum: float, eps: float, slope: float):
+        y, mean, invstd = batchnorm_rows_fwd_train(x2, weight, bias, running_mean, running_var, momentum, eps, slope)
+        ctx.save_for_backward(x2, y, mean, invstd, weight)
+        ctx.slope = slope
+        ctx.has_bias = bias is not None
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, y, mean, invstd, weight = ctx.saved_tensors
+        dy2 = dy if dy.dim() == 2 and dy.stride(1) == 1 and _rows_apart(dy) else dy.contiguous()
+        want_w = weight is not None and ctx.needs_input_grad[1]
+        want_b = ctx.has_bias and ctx.needs_input_grad[2]
+        dx, dw, db = batchnorm_rows_bwd(dy2, y, x2, weight, mean, invstd, ctx.slope, want_w, want_b)
+        return dx if ctx.needs_input_grad[0] else None, dw, db, None, None, None, None, None
+
+
+def batchnorm_rows(x: torch.Tensor, weight, bias, running_mean, running_var, training: bool, momentum: float = 0.1,
+                   eps: float = 1e-5, negative_slope: float = 0.2) -> torch.Tensor:
+    """leaky_relu(batch_norm(x), negative_slope) with the channels on x's LAST
+    axis and the statistics over all other axes: the reference's
+    x.permute(0, 2, 1) -> nn.BatchNorm1d -> permute back -> F.leaky_relu
+    (deep_rp_robust_gcn.py:39-45, 57-63) without the transposed copies.
+    x [..., C] float32 on the device (bfloat16 is refused); weight / bias [C]
+    or None (1 / 0); running_mean / running_var [C] or None.
+
+    training (or no running statistics): batch statistics, accumulated in
+    fp64 (grl_bn_rows_fwd_train), the running buffers updated in place, one
+    autograd node whose backward is one grl_bn_rows_bwd call.  Results are the
+    same bits run to run and on every device.  At least two rows.
+    Inference with gradients disabled: one pass (grl_bn_rows_fwd_eval).
+    Inference with gradients enabled is not a hot path: torch's F.batch_norm +
+    F.leaky_relu on the 2-D view, differentiable through torch."""
+    _require_device(x, "batchnorm_rows input")
+    if x.dtype != torch.float32:
+        raise _lib.GrlError(f"batchnorm_rows: a float32 input (got {x.dtype}); bfloat16 tables are not supported")
+    if x.dim() < 1:
+        raise _lib.GrlError("batchnorm_rows: x must have a channel axis")
+    lead, C = x.shape[:-1], x.shape[-1]
+    x2 = _rows_view(x)
+    if x2.shape[0] > 1 and not _rows_apart(x2):
+        x2 = x2.contiguous()
+    if training or running_mean is None or running_var is None:
+        if x2.shape[0] == 1:
+            raise _lib.GrlError("batchnorm_rows: training needs more than one value per channel (got 1 row)")
+        y = _BatchNormRows.apply(x2, weight, bias, running_mean, running_var, float(momentum), float(eps),
+                                 float(negative_slope))
+    elif not torch.is_grad_enabled():
+        y = batchnorm_rows_fwd_eval(x2, weight, bias, running_mean, running_var, eps, negative_slope)
+    else:
+        y = torch.nn.functional.leaky_relu(
+            torch.nn.functional.batch_norm(x2, running_mean, running_var, weight, bias, False, 0.0, eps),
+            negative_slope)
+    return y.view(*lead, C)
+
+
 # ------------------------------------------------------- row-local linears
 def linear_fwd_ex(X2: torch.Tensor, W: torch.Tensor, w_layout: int, b, relu: bool, path_rows: int = 0,
                   out: torch.Tensor = None) -> torch.Tensor:

@@ -239,6 +239,75 @@ int grl_feature_dropout_bf16(const uint16_t* x, int64_t ldx, uint16_t* out,
                              int64_t row0, const GrlDropEdge* de,
                              grl_stream_t stream);
 
+/*
+ * BatchNorm1d over node rows with its LeakyReLU: the reference's
+ * x.permute(0, 2, 1) -> nn.BatchNorm1d -> permute back -> F.leaky_relu of
+ * GCNBlock / EmbeddingBlock (gnn/models/networks/deep_rp_robust_gcn.py:39-45,
+ * 57-63) on the row-major table as it lies, without a transposed copy.
+ * Every table is fp32 [rows][ld*] with ld* >= cols (a column slice of a wider
+ * table is a valid operand); gamma, beta, the statistics and the parameter
+ * gradients are contiguous fp32 [cols].  Channel c's statistics run over all
+ * `rows` values of column c.  Sums accumulate in fp64 (a widened fp32 value
+ * and the product of two are exact there) per row block, the blocks' partials
+ * are added in block order by one thread per column, and mean / invstd are
+ * rounded to fp32 once.  The row blocks are a function of (rows, cols) only,
+ * never of the device, and nothing is atomic: the same input gives the same
+ * bits run to run and machine to machine.  Rows take 16 B per lane where
+ * cols and every row stride are multiples of 4 and every table pointer is
+ * 16-B aligned, else 4 B per lane -- the same bits either way.  Any
+ * cols >= 1.  rows == 0 or cols == 0: GRL_OK, nothing is launched.  Errors
+ * (GRL_E_INVALID): a negative size, a row stride below cols, a NULL table, a
+ * workspace below grl_bn_rows_workspace_size or not 8-B aligned.  No
+ * allocation, no host sync.
+ */
+
+/* Bytes of the partials workspace of grl_bn_rows_fwd_train and
+ * grl_bn_rows_bwd for a [rows][cols] table (0 for an empty one).          */
+size_t grl_bn_rows_workspace_size(int64_t rows, int32_t cols);
+
+/* Training forward: save_mean[c] = mean of column c, save_invstd[c] =
+ * 1 / sqrt(biased variance + eps), then
+ *   y = leaky(gamma * (x - mean) * invstd + beta, slope),
+ * leaky(v, s) = v > 0 ? v : v * s.  gamma / beta NULL = 1 / 0.  Where non-NULL
+ * the running statistics are updated in place as torch does:
+ *   running_mean = (1 - momentum) * running_mean + momentum * mean
+ *   running_var  = (1 - momentum) * running_var
+ *                  + momentum * variance * rows / (rows - 1).
+ * rows == 1 is GRL_E_INVALID (torch refuses one value per channel in
+ * training).  Three kernels: statistics, finalize, apply; x is read twice and
+ * y written once.                                                          */
+int grl_bn_rows_fwd_train(const float* x, int64_t ldx, int64_t rows, int32_t cols,
+                          const float* gamma, const float* beta, float eps,
+                          float slope, float momentum, float* running_mean,
+                          float* running_var, float* y, int64_t ldy,
+                          float* save_mean, float* save_invstd, void* workspace,
+                          size_t ws_bytes, grl_stream_t stream);
+
+/* Inference forward, one pass:
+ *   y = leaky(gamma * (x - running_mean) / sqrt(running_var + eps) + beta, slope)
+ * with the per-column scale formed in the kernel.  gamma / beta NULL = 1 / 0.
+ * y may alias x.                                                           */
+int grl_bn_rows_fwd_eval(const float* x, int64_t ldx, int64_t rows, int32_t cols,
+                         const float* gamma, const float* beta,
+                         const float* running_mean, const float* running_var,
+                         float eps, float slope, float* y, int64_t ldy,
+                         grl_stream_t stream);
+
+/* Backward of grl_bn_rows_fwd_train from its x, y, save_mean, save_invstd.
+ *   g = dy * (y > 0 ? 1 : slope)   (the sign of y is the pre-activation's for
+ *       every slope >= 0; y == 0 takes slope, as torch's leaky_relu backward)
+ *   xhat = (x - mean) * invstd
+ *   dbeta = sum_r g, dgamma = sum_r g * xhat        (written where non-NULL)
+ *   dx = gamma * invstd * (g - dbeta / rows - xhat * dgamma / rows)
+ * gamma NULL = 1.  dx may alias dy.  Three kernels: partial sums, finalize,
+ * apply.  slope must be the forward's.                                     */
+int grl_bn_rows_bwd(const float* dy, int64_t lddy, const float* y, int64_t ldy,
+                    const float* x, int64_t ldx, int64_t rows, int32_t cols,
+                    const float* gamma, const float* save_mean,
+                    const float* save_invstd, float slope, float* dx,
+                    int64_t lddx, float* dgamma, float* dbeta, void* workspace,
+                    size_t ws_bytes, grl_stream_t stream);
+
 /* keep[i] = 1 if id_base + i survives DropEdge `de`, else 0 (i < count).
  * Exposes the fused mask for parity checks against the dense reference
  * (the mask nn.Dropout would draw over A_pre, drop_robust_gcn.py:76).    */
